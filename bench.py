@@ -17,7 +17,14 @@ latency extrema, inside the timed region.
 Prints ONE JSON line on rank 0 (contract in the task statement), with
 `roofline` (dominant kernel = isim_walk, algorithmic bytes per launch =
 16 B/trace records + program + stats, live HIP-event timing on the launch
-stream) and `cpu_baseline` (the C oracle, OpenMP, bounded sample, rank 0).
+stream: figures of the timed steps themselves).
+
+A plain run sets up, warms up, times the K steps and prints the line.
+`--full` adds the legs that take runs of their own: `cpu_baseline` (the C
+oracle, OpenMP, bounded sample, rank 0), config 3's mode-B legs, the
+wave-interpreter leg of the dynamic walks and config 1's error path.
+`--dump-outputs DIR` writes what the last timed step handed its caller
+(dump_outputs) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -106,6 +113,13 @@ def parse():
                     help="dynamic walks: skip the per-service duration histograms")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--cpu-traces", type=int, default=0, help="cpu_baseline sample size (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: cpu_baseline, c3's mode-B legs, the "
+                         "wave-interpreter leg of c3p / c3s / c4w / cdag, c1's error path (each still has its "
+                         "--no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (records, stats, DES table) as "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
     args.des_auto_batch = False  # c5 with the default batch: shrink it to the device's free HBM
     if not args.prob:
@@ -255,6 +269,63 @@ def cpu_baseline_des(json_text: str, params, mean_ns: int, n_traces: int):
                       f"(replica r: trace ids from r*{n}, arrivals from time 0), event-driven C oracle "
                       f"oracle/des_oracle.c (binary heap, sequential per replica), {dt:.1f} s",
             "hop_visits_per_s": hops / dt}
+
+
+DUMP_ROWS = 1 << 19    # records kept by --dump-outputs (16 MB as float64 + indices)
+DUMP_WORDS = 1 << 20   # words kept of the stats buffer / the DES table (8 MB each + indices)
+
+
+def dump_outputs(out_dir, recs, stats, folded, table=None):
+    """--dump-outputs: what the caller of the timed path holds after the last
+    timed step, as float64 .npy files (counts and per-trace values are below
+    2^53 and exact; a sum past it, like sum_latency, is rounded to 53 bits):
+
+    records.npy        (n, 3): latency_ns, hops, status_err of the last step's
+                       records; above DUMP_ROWS rows a fixed sample (seed 0,
+                       sorted) whose row numbers are records_index.npy
+    summary.npy        n_traces, sum_latency, sum_hops, sum_err_hops, n_500,
+                       min_latency, max_latency of the stats buffer
+    stats.npy          the stats buffer's words (accumulated over the timed
+                       steps, as the caller passes one buffer to every step;
+                       above DUMP_WORDS a fixed sample, stats_index.npy)
+    des_table.npy      DES configs: the per-replica table, likewise
+
+    The graph, the parameters and the trace ids are fixed by the arguments,
+    so two builds run with the same arguments write comparable files."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(n, keep):
+        if n <= keep:
+            return None
+        return np.sort(np.random.default_rng(0).integers(0, n, keep))
+
+    def words(name, t):
+        idx = sample(t.numel(), DUMP_WORDS)
+        if idx is not None:
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy().view(np.uint64).astype(np.float64))
+
+    if recs is not None:
+        idx = sample(recs.shape[0], DUMP_ROWS)
+        r = recs
+        if idx is not None:
+            np.save(os.path.join(out_dir, "records_index.npy"), idx.astype(np.float64))
+            r = recs[torch.from_numpy(idx).to(recs.device)]
+        r = r.cpu().numpy().view(np.uint64)
+        out = np.empty((r.shape[0], 3), np.float64)
+        out[:, 0] = r[:, 0]
+        out[:, 1] = r[:, 1] & np.uint64(0xFFFFFFFF)
+        out[:, 2] = r[:, 1] >> np.uint64(32)
+        np.save(os.path.join(out_dir, "records.npy"), out)
+    np.save(os.path.join(out_dir, "summary.npy"),
+            np.array([folded[k] for k in ("n_traces", "sum_latency", "sum_hops", "sum_err_hops", "n_500",
+                                          "min_latency", "max_latency")], np.float64))
+    words("stats", stats)
+    if table is not None:
+        words("des_table", table)
 
 
 def main_des(args, h, json_text, desc, params, rank, world, dev, multi=None, merge_label=""):
@@ -426,7 +497,9 @@ def main_des(args, h, json_text, desc, params, rank, world, dev, multi=None, mer
         "hop_visits_per_s": value * folded["sum_hops"] / total,
         "n_500_frac": folded["n_500"] / total,
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, recs, stats, folded, table)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline_des(json_text, params, args.mean_interarrival_ns, args.cpu_traces)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -737,17 +810,20 @@ def main():
         "hop_visits_per_s": value * hops_per_trace,
         "n_500_frac": folded["n_500"] / total,
     }
-    if args.config == "c3" and args.mode == "A" and not args.no_mode_b:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, recs, stats, folded)
+    # the legs beside the headline figure run only with --full
+    if args.full and args.config == "c3" and args.mode == "A" and not args.no_mode_b:
         line.update(mode_b_legs(args, json_text, rank, world, dev, multi))
-    if args.config in ("c3p", "c3s", "c4w", "cdag") and not args.no_wave_leg:
+    if args.full and args.config in ("c3p", "c3s", "c4w", "cdag") and not args.no_wave_leg:
         line["wave_walk"] = wave_walk_leg(args, json_text, params, rank, world, dev, multi)
         line["speedup_vs_wave_walk"] = value / line["wave_walk"]["value"]
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # config 1 is defined on the CPU interpreter: time it on the whole
         # 1M-trace workload; other configs on a bounded sample
         n_cpu = args.cpu_traces or (B if args.config == "c1" else 0)
         line["cpu_baseline"] = cpu_baseline(json_text, params, n_cpu, 0)
-    if args.config == "c1":
+    if args.full and args.config == "c1":
         line["error_path"] = c1_error_path(args, json_text, params, rank, world, dev, multi)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -14,7 +14,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   tail -2 $O/tests.log
 fi
 for c in ${CFGS:-c5p c4d}; do
-  ISIM_DES_DEBUG=1 timeout -k 10 400 python -u bench.py --config $c --steps ${STEPS:-3} --warmup 1 ${BENCH_ARGS:---no-cpu} \
+  ISIM_DES_DEBUG=1 timeout -k 10 400 python -u bench.py --full --config $c --steps ${STEPS:-3} --warmup 1 ${BENCH_ARGS:---no-cpu} \
     > $O/bench_$c.log 2>&1 || { echo "bench $c failed"; tail -20 $O/bench_$c.log; exit 2; }
   grep '^{' $O/bench_$c.log | tail -1
   if [ "${PROF:-1}" = 1 ]; then

@@ -8,7 +8,7 @@ O=gpurun_out/mb
 VAR=${VAR:-istio-isotope_amd/isim/libisim_oldwalk.so}
 for rep in 1 2; do
 for lib in "" "$VAR"; do
-  timeout -k 10 300 env ${lib:+ISIM_LIB=$lib} python bench.py --no-cpu --steps 5 --warmup 2 --mode-b-steps 5 > $O/b.log 2>&1 || { echo B_FAIL $lib; tail $O/b.log; exit 7; }
+  timeout -k 10 300 env ${lib:+ISIM_LIB=$lib} python bench.py --full --no-cpu --steps 5 --warmup 2 --mode-b-steps 5 > $O/b.log 2>&1 || { echo B_FAIL $lib; tail $O/b.log; exit 7; }
   grep '^{' $O/b.log | python -c "import json,sys;d=json.loads(sys.stdin.read());print('[${lib:-current}]', 'A', round(d['value']/1e6,1), 'B', round(d['mode_b']['value']/1e6,1), 'ratio', round(d['mode_b']['value']/d['value'],3), 'Binf', round(d['mode_b_informative']['value']/1e6,1), 'kms', round(d['mode_b']['kernel_ms'],2))"
 done
 done

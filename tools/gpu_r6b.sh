@@ -10,7 +10,7 @@ rc=$?
 grep -E "FAILED|ERROR|passed|failed" $O/tests.log | tail -5
 [ $rc -eq 0 ] || exit $rc
 for c in c3 c3p c3s c4w cdag c4; do
-timeout -k 10 600 python bench.py --config $c > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 6; }
+timeout -k 10 600 python bench.py --full --config $c > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 6; }
 grep '^{' $O/bench_$c.log | tail -1 | python -c "import json,sys;d=json.loads(sys.stdin.read());print('$c', d['value'], d['roofline']['kernel_ms'], {k:(d[k]['value'],d[k]['kernel_ms'],d[k]['kernel_kind']) for k in ('mode_b','mode_b_informative') if k in d}, d.get('speedup_vs_wave_walk'))"
 done
 LIBS="libisim.so libisim_nohist.so libisim_nosink.so" CFG="--config c4" \

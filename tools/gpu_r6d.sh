@@ -9,6 +9,6 @@ timeout -k 10 900 python -u -m pytest -x -q --timeout 400 --timeout-method threa
 rc=$?
 tail -3 $O/tests.log
 [ $rc -eq 0 ] || { grep -E "FAILED|Error" $O/tests.log | head; exit $rc; }
-timeout -k 10 600 python bench.py --config c4d > $O/bench_c4d.log 2>&1 || { tail -20 $O/bench_c4d.log; exit 6; }
+timeout -k 10 600 python bench.py --full --config c4d > $O/bench_c4d.log 2>&1 || { tail -20 $O/bench_c4d.log; exit 6; }
 grep '^{' $O/bench_c4d.log | tail -1 | python -c "import json,sys;d=json.loads(sys.stdin.read());print('c4d', d['value'], d['ms_per_step'], d['config']['des_passes_per_step'], d['config']['des_syncs_per_step'], d['roofline']['frac'])"
 bash tools/gpu_c4d_trace.sh 2>&1 | tail -12

@@ -11,7 +11,7 @@ tail -3 $O/gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 7; }
 tail -2 $O/smoke.log
 for c in c4 c3p c3s c4w cdag; do
-timeout -k 10 600 python bench.py --config $c > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 6; }
+timeout -k 10 600 python bench.py --full --config $c > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 6; }
 grep '^{' $O/bench_$c.log | tail -1 | python -c "import json,sys;d=json.loads(sys.stdin.read());print('$c', d['value'], d['roofline']['kernel_ms'], d.get('speedup_vs_wave_walk'))"
 done
 SETS="c3p|--config_c3p c3s|--config_c3s c4|--config_c4 c4w|--config_c4w cdag|--config_cdag" bash tools/gpu_r6_prof.sh

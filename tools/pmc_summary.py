@@ -79,8 +79,8 @@ def main(src, rnd, name):
         "round": int(rnd.lstrip("r")),
         "config": name,
         "batch": n,
-        "command": f"tools/profile_cfg.sh {name}: rocprofv3 --kernel-trace --stats -- python3 bench.py "
-                   f"{bench_args(src)}; PMC passes: --pmc FETCH_SIZE | WRITE_SIZE | SQ_* (bench.py ... --steps 3 "
+        "command": f"tools/profile_cfg.sh {name}: rocprofv3 --kernel-trace --stats -- python3 bench.py --full "
+                   f"{bench_args(src)}; PMC passes: --pmc FETCH_SIZE | WRITE_SIZE | SQ_* (bench.py --full ... --steps 3 "
                    "--warmup 1 --no-cpu)",
         "kernel": walk["Name"],
         "kernel_avg_ns": kernel_ns,

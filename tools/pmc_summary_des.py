@@ -73,7 +73,7 @@ def main(src, rnd, name):
     calls = sum(int(r["Calls"]) for r in stats if mine(name, r["Name"]))
     out = {
         "round": int(rnd.lstrip("r")), "config": name, "batch": bench["config"]["traces_per_rank_per_step"],
-        "command": f"tools/profile_des.sh {name}: rocprofv3 --kernel-trace --stats -- python3 bench.py --config "
+        "command": f"tools/profile_des.sh {name}: rocprofv3 --kernel-trace --stats -- python3 bench.py --full --config "
                    f"{name}; PMC passes --pmc FETCH_SIZE | WRITE_SIZE | SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES "
                    f"GRBM_GUI_ACTIVE (bench.py --config {name} --steps 1 --warmup 1 --no-cpu)",
         "kernel_ns_per_step": ns / n_steps,

@@ -11,7 +11,7 @@ NAME=$1
 O=$R/gpurun_out/prof_$NAME
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- python3 $R/bench.py --config $NAME > $O/stats.log 2>&1 || exit 11
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- python3 $R/bench.py --full --config $NAME > $O/stats.log 2>&1 || exit 11
 for p in "fetch FETCH_SIZE" "write WRITE_SIZE" "sq SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   set -- $p; pn=$1; shift
   timeout -k 10 400 rocprofv3 --kernel-trace --pmc "$@" -d $O/$pn -o run --output-format csv -- python3 $R/bench.py --config $NAME --steps 1 --warmup 1 --no-cpu > $O/$pn.log 2>&1 || exit 12
