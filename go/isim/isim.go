@@ -155,6 +155,45 @@ func (h *Handler) LastDesBatch() (DesBatch, error) {
 	return DesBatch{uint32(st.passes), uint32(st.syncs), uint64(st.items)}, nil
 }
 
+// Quantiles is one class's exact latency percentiles (isim_latency_quantiles):
+// the records in the class and, per requested quantile, the nearest-rank
+// latency in ns (all 0 for an empty class).
+type Quantiles struct {
+	Count  uint64
+	Values []uint64
+}
+
+// LatencyQuantiles computes exact percentiles of recs' latencies on GPU
+// `device`, for every record, the 200s and the 500s (C.ISIM_Q_ALL /
+// ISIM_Q_200 / ISIM_Q_500).  qPpm are parts per million (p99.9 = 999000), at
+// most C.ISIM_MAX_QUANTILES of them, in any order.
+func LatencyQuantiles(device int, recs []TraceRecord, qPpm []uint32) ([3]Quantiles, error) {
+	var res [3]Quantiles
+	var rp *TraceRecord
+	if len(recs) > 0 {
+		rp = &recs[0]
+	}
+	var qp *C.uint32_t
+	if len(qPpm) > 0 {
+		qp = (*C.uint32_t)(unsafe.Pointer(&qPpm[0]))
+	}
+	nq := len(qPpm)
+	if nq < 1 || nq > C.ISIM_MAX_QUANTILES {
+		// libisim's EINVAL and message; the output is never written
+		return res, lastErr(C.isim_latency_quantiles(C.int(device), rp, C.uint64_t(len(recs)), qp, C.uint32_t(nq), nil))
+	}
+	out := make([]uint64, 3*(1+nq)) // ISIM_Q_OUT_WORDS (cgo sees no function-like macros)
+	rc := C.isim_latency_quantiles(C.int(device), rp, C.uint64_t(len(recs)), qp, C.uint32_t(nq), u64ptr(out))
+	if rc != C.ISIM_OK {
+		return res, lastErr(rc)
+	}
+	for c := range res {
+		row := out[c*(1+nq) : (c+1)*(1+nq)]
+		res[c] = Quantiles{Count: row[0], Values: row[1:]}
+	}
+	return res, nil
+}
+
 type Multi struct{ m *C.isim_multi }
 
 // u64ptr passes an empty slice as NULL (libisim then reports EINVAL) instead

@@ -462,6 +462,43 @@ ISIM_API int isim_serve_multi(isim_handler *h, isim_multi *m, uint64_t trace_beg
 ISIM_API int isim_stats_merge(const isim_handler *h, uint64_t *dst, const uint64_t *src);
 ISIM_API int isim_des_table_merge(const isim_handler *h, uint64_t *dst, const uint64_t *src);
 
+/* ---- exact latency percentiles from per-trace records ----
+ * The Fortio client's report (p50 / p75 / p90 / p99 / p99.9) as exact order
+ * statistics of isim_trace_rec.latency_ns, computed on the device from the
+ * records a walk or a DES batch just wrote: an MSD radix select, every class
+ * and quantile in one sweep per 8-bit digit, at most 9 reads of the records.
+ * Classes: every record, the 200s and the 500s (status_err bit 31).  For each
+ * class c, out[c][0] is the count N_c of its records and out[c][1 + i] the
+ * k-th smallest latency_ns among them, k = isim_quantile_rank(N_c, q_ppm[i])
+ * (nearest rank); all 0 when N_c is 0.  The ranks are computed on the device
+ * from the counts.  Any u64 latency is valid; q_ppm need not be sorted and may
+ * repeat; n_records 0 gives all zeros.  ISIM_EINVAL: n_q 0 or above
+ * ISIM_MAX_QUANTILES, a q_ppm above 1,000,000, n_records above 2^40, a
+ * workspace below isim_quantiles_workspace_bytes(n_q), a null d_out or
+ * d_workspace, a records pointer that is not 16-byte aligned. */
+#define ISIM_MAX_QUANTILES 16
+#define ISIM_Q_ALL 0   /* every record */
+#define ISIM_Q_200 1   /* status_err bit31 clear */
+#define ISIM_Q_500 2   /* status_err bit31 set  */
+/* out: u64[3][1 + n_q]; per class: matching-record count, then the n_q values
+   (all 0 when the count is 0) */
+#define ISIM_Q_OUT_WORDS(n_q) (3 * (1 + (uint64_t)(n_q)))
+
+/* nearest rank, 1-based: k = max(1, ceil(q_ppm * n / 1e6)); n in 1..2^40, q_ppm in 0..1000000 */
+ISIM_API int isim_quantile_rank(uint64_t n, uint32_t q_ppm, uint64_t *k);       /* host only, no GPU */
+ISIM_API int isim_quantiles_workspace_bytes(uint32_t n_q, uint64_t *bytes);     /* host only */
+/* On the current device, asynchronously on hip_stream, like isim_serve_device:
+ * no host synchronisation, no allocation, graph-capturable from the first
+ * call.  q_ppm is a host array, copied at the call.  The call clears the
+ * workspace state it needs: a dirty workspace may be reused (calls that share
+ * one must be ordered, e.g. on one stream). */
+ISIM_API int isim_latency_quantiles_device(const isim_trace_rec *d_records, uint64_t n_records,
+                                           const uint32_t *q_ppm, uint32_t n_q,   /* host array, copied at the call */
+                                           uint64_t *d_out, void *d_workspace, uint64_t workspace_bytes,
+                                           void *hip_stream);
+ISIM_API int isim_latency_quantiles(int device, const isim_trace_rec *h_records, uint64_t n_records,
+                                    const uint32_t *q_ppm, uint32_t n_q, uint64_t *h_out);  /* synchronous convenience */
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,3 +10,5 @@ from .sim import REC_DTYPE, Handler, SimParams, decode_stats, handler_from_servi
 from .yamljson import yaml_to_json  # noqa: F401
 from . import prometheus  # noqa: F401
 from .des import DesHandler  # noqa: F401
+from .quantiles import (DEFAULT_Q, latency_quantiles, latency_quantiles_device, quantile_rank,  # noqa: F401
+                        quantiles_out_words, quantiles_workspace_bytes)

@@ -51,6 +51,9 @@ SVC_DUR_WORDS = 2 * N_PROM + 2
 DES_COUNT, DES_SUM_WAIT, DES_MAX_WAIT, DES_SUM_HOLD = SVC_DUR_WORDS, SVC_DUR_WORDS + 1, SVC_DUR_WORDS + 2, SVC_DUR_WORDS + 3
 DES_ROW_WORDS = SVC_DUR_WORDS + 4
 DES_FLAG_WIDE = 1  # isim_des_params.flags: 64-bit rows
+# exact latency percentiles (isim.h ISIM_Q_*): out is u64[3][1 + n_q], per class the count then the values
+MAX_QUANTILES = 16
+Q_ALL, Q_200, Q_500 = 0, 1, 2
 
 
 class IsimError(RuntimeError):
@@ -159,6 +162,11 @@ SIGNATURES = {
     "isim_serve_multi": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint64, _VP, _VP]),
     "isim_stats_merge": (C.c_int, [_VP, _VP, _VP]),
     "isim_des_table_merge": (C.c_int, [_VP, _VP, _VP]),
+    "isim_quantile_rank": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "isim_quantiles_workspace_bytes": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64)]),
+    "isim_latency_quantiles_device": (C.c_int, [_VP, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, _VP, _VP,
+                                                C.c_uint64, _VP]),
+    "isim_latency_quantiles": (C.c_int, [C.c_int, _VP, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, _VP]),
 }
 
 _lib = None
