@@ -163,6 +163,28 @@ struct DesPlan {
   uint32_t rounds() const { return (uint32_t)arr_off.size() - 1; }
 };
 
+// Fixed-point passes of a cyclic schedule before a batch is dropped (both engines).
+constexpr uint32_t kMaxPasses = 256;
+
+// The workspace of one static-engine batch (des_layout.h: des_layout).
+namespace dev {
+struct ChainState;
+}
+struct DesBufs {
+  void *W, *WF, *BK;                 // rows [n_pos][ld] (starts, finishes), [steps][ld] of u32 or u64
+  uint64_t *A, *blk;                 // [N] arrival times, chunk sums
+  uint32_t *E;                       // [N] per-trace 500 count
+  uint32_t *tickets, *prog;          // queue passes: ticket counters [4 x rounds], published chunk counts [n_pos]
+  dev::ChainState *chain;            // chained-scan states [n_pos][chunks]
+  uint64_t pass_zero_bytes;          // tickets, prog and chain: zeroed before every pass
+  uint32_t *ovf, *changed;           // narrow rows: overflow flag; cyclic schedules: changed flag (ovf + 1)
+  uint64_t *stage;                   // staged stats (stats_words) + table
+  uint32_t *stbits;                  // own error status bits [n_pos][words of 32 traces]
+  uint64_t *keys_a, *keys_b;         // sort path: keys in and out,
+  uint32_t *vals_a, *vals_b;         // values in and out,
+  void *sort_tmp;                    // rocPRIM's temporary storage
+};
+
 // Device buffers and sizes of one DES batch (des.hip: des_launch).
 struct DesLaunch {
   const DesPlan *plan;               // host copy (the schedule)
@@ -170,15 +192,7 @@ struct DesLaunch {
   const uint32_t *d_child, *d_fast_pos, *d_sort_pos, *d_fin_pos, *d_arr_ops, *d_zero_pos;
   const uint32_t *d_pipe;            // pipe_pos then pipe_dep
   const uint32_t *d_mult;            // per slot: calls per trace (executed-call counters)
-  // workspace parts (des_carve)
-  void *W, *WF, *BK;                 // rows [n_pos][ld] (starts, finishes), [steps][ld] of u32 or u64
-  uint64_t *A, *blk;                 // [N] arrival times, chunk sums
-  uint32_t *E;                       // [N] per-trace 500 count
-  void *chain;                       // chained-scan states of the down pass (des_chain_bytes)
-  uint32_t *ovf;                     // narrow rows: overflow flag
-  uint64_t *stage;                   // narrow rows: staged stats (stats_words) + table
-  uint32_t *stbits;                  // own error status bits [n_pos][words of 32 traces]
-  void *sort_ws;                     // sort path (keys, values, radix-sort temp)
+  DesBufs ws;                        // workspace parts (des_carve)
   // caller buffers
   uint64_t *d_stats, *d_table;
   isim_trace_rec *d_records;         // may be null
@@ -189,8 +203,7 @@ struct DesLaunch {
   bool wide;                         // u64 rows (ISIM_DES_FLAG_WIDE); else u32 rows + overflow retry
 };
 
-// Workspace bytes for a batch of n traces (every part 256-B aligned; rows
-// sized for u64 so one workspace serves both row widths).
+// Workspace bytes for a batch of n traces: a sizing run of des_layout (des_layout.h).
 uint64_t des_workspace_bytes(const DesPlan &plan, uint64_t n, uint64_t stats_words, uint64_t table_rows);
 // Points L's workspace parts into `workspace` (L.plan, n_traces, stats_words, table_rows set).
 void des_carve(DesLaunch &L, void *workspace);
@@ -205,9 +218,6 @@ uint32_t des_spin_limit();
 void des_set_spin_limit(uint32_t polls);
 // Bit of ISIM_ST_DES_RETRY's high word: batches dropped for a device fault
 constexpr uint64_t kDesFaultUnit = 1ull << 32;
-// Chained-scan workspace of the down pass: a ticket counter per launch, then
-// one 32-byte state per (position, chunk of 4096 traces); zeroed per batch.
-uint64_t des_chain_bytes(const DesPlan &plan, uint64_t n);
 
 // Rows one trace reads and writes in a batch's queue and finish passes (one
 // pass of a cyclic schedule): what des.hip's kernels move per trace, 4 or 8

@@ -40,7 +40,7 @@
 #include <type_traits>
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "des.h"
+#include "des_layout.h"
 #ifndef ISIM_DES_N32_FOLD
 #define ISIM_DES_N32_FOLD 1  // 32-bit queue finish: waits summed in pairs, duration sums derived, 500s under one branch
 #endif
@@ -1479,12 +1479,7 @@ __global__ void __launch_bounds__(kDownThreads, ISIM_DES_DOWN_WAVES) des_down_mi
 // a decoupled look-back over their max-plus maps.  Workgroups take tickets in
 // launch order (position-major, chunk-minor), so every chunk they wait on
 // has started.
-struct ChainState {
-  uint64_t B, C;   // B: the chunk's largest key a_t - t h, as int64 (flag >= 1); C unused
-  uint64_t P;      // the largest key up to and including the chunk (flag 2)
-  uint32_t flag, pad;
-};
-static_assert(sizeof(ChainState) == 32, "ChainState is 32 bytes");
+// (ChainState, one per (position, chunk): des_layout.h)
 
 // the ticket of a chained-scan workgroup: (position, chunk) in launch order
 __device__ __forceinline__ uint32_t chain_ticket(const DesK &k) {
@@ -2457,67 +2452,29 @@ static size_t sort_temp_bytes(uint64_t m) {
   return bytes;
 }
 
-static uint64_t al256(uint64_t b) { return (b + 255) & ~255ull; }
-static uint64_t row_ld(uint64_t n) { return (n + 15) & ~15ull; }
-static uint64_t chain_tickets(const DesPlan &plan) { return 4ull * plan.rounds(); }
-static uint64_t status_wpr(uint64_t n) { return (((n + 31) / 32) + 15) & ~15ull; }
+static_assert(kDesArrChunk == dev::kDesChunk && kDesDownChunk == dev::kDownChunk, "des_layout.h chunk sizes");
 
-// chained and pipelined down passes: tickets, per-position published chunk
-// counts, chain states (all zeroed before every pass)
-uint64_t des_chain_bytes(const DesPlan &plan, uint64_t n) {
-  const uint64_t chunks = (n + dev::kDownChunk - 1) / dev::kDownChunk;
-  return al256(chain_tickets(plan) * 4) + al256(plan.pos.size() * 4) +
-         (uint64_t)plan.pos.size() * chunks * sizeof(dev::ChainState);
-}
-
-// Workspace parts, in order (256-B aligned): W and BK rows sized for u64,
-// A, E, chunk sums, chain states, overflow flag, staged stats + table, sort path.
 uint64_t des_workspace_bytes(const DesPlan &plan, uint64_t n, uint64_t stats_words, uint64_t table_rows) {
-  const uint64_t nblk = (n + dev::kDesChunk - 1) / dev::kDesChunk;
-  const uint64_t ld = row_ld(n);
-  const uint64_t m = (uint64_t)plan.max_sort_pos * n;
-  const uint64_t sort = m ? 2 * al256(m * 8) + 2 * al256(m * 4) + al256(sort_temp_bytes(m)) : 0;
-  return 2 * al256((uint64_t)plan.pos.size() * ld * 8) + al256((uint64_t)plan.steps.size() * ld * 8) + al256(n * 8) +
-         al256(n * 4) + al256((nblk + 1) * 8) + al256(des_chain_bytes(plan, n)) + 256 +
-         al256((stats_words + table_rows * ISIM_DES_ROW_WORDS) * 8) +
-         al256((uint64_t)plan.pos.size() * status_wpr(n) * 4) + sort;
+  Arena sizing;
+  DesBufs b;
+  des_layout(sizing, b, plan, n, stats_words, table_rows, sort_temp_bytes((uint64_t)plan.max_sort_pos * n));
+  return sizing.bytes();
 }
 
 void des_carve(DesLaunch &L, void *workspace) {
-  const DesPlan &plan = *L.plan;
-  const uint64_t n = L.n_traces, ld = row_ld(n);
-  char *ws = (char *)workspace;
-  auto take = [&](uint64_t bytes) {
-    char *p = ws;
-    ws += al256(bytes);
-    return p;
-  };
-  L.W = take((uint64_t)plan.pos.size() * ld * 8);
-  L.WF = take((uint64_t)plan.pos.size() * ld * 8);
-  L.BK = take((uint64_t)plan.steps.size() * ld * 8);
-  L.A = (uint64_t *)take(n * 8);
-  L.E = (uint32_t *)take(n * 4);
-  L.blk = (uint64_t *)take(((n + dev::kDesChunk - 1) / dev::kDesChunk + 1) * 8);
-  L.chain = take(des_chain_bytes(plan, n));
-  L.ovf = (uint32_t *)take(4);
-  L.stage = (uint64_t *)take((L.stats_words + (uint64_t)L.table_rows * ISIM_DES_ROW_WORDS) * 8);
-  L.stbits = (uint32_t *)take((uint64_t)plan.pos.size() * status_wpr(n) * 4);
-  L.sort_ws = ws;
+  Arena carving(workspace);
+  des_layout(carving, L.ws, *L.plan, L.n_traces, L.stats_words, L.table_rows,
+             sort_temp_bytes((uint64_t)L.plan->max_sort_pos * L.n_traces));
 }
 
 // The rounds of one batch with row type T: step begins,
 // queues (fast: in place; sort path: radix sort first), finishes.
 template <typename T>
-static int des_rounds(const DesLaunch &L, dev::DesK k, uint32_t *tickets, hipStream_t stream) {
+static int des_rounds(const DesLaunch &L, dev::DesK k, hipStream_t stream) {
   using namespace dev;
   const DesPlan &pl = *L.plan;
-  const uint64_t m_max = (uint64_t)pl.max_sort_pos * L.n_traces;
-  char *sw = (char *)L.sort_ws;
-  uint64_t *keys_a = (uint64_t *)sw, *keys_b = (uint64_t *)(sw + al256(m_max * 8));
-  uint32_t *vals_a = (uint32_t *)(sw + 2 * al256(m_max * 8));
-  uint32_t *vals_b = (uint32_t *)(sw + 2 * al256(m_max * 8) + al256(m_max * 4));
-  void *sort_tmp = sw + 2 * al256(m_max * 8) + 2 * al256(m_max * 4);
-  const size_t sort_tmp_bytes = sort_temp_bytes(m_max);
+  const DesBufs &B = L.ws;
+  const size_t sort_tmp_bytes = sort_temp_bytes((uint64_t)pl.max_sort_pos * L.n_traces);
   k.sort_pos = L.d_sort_pos;
   // (position or row) x trace-range blocks: enough to fill the chip, >= 256 traces each
   // and at most ISIM_DES_MAX_SPLITS per position: every block flushes its
@@ -2547,7 +2504,7 @@ static int des_rounds(const DesLaunch &L, dev::DesK k, uint32_t *tickets, hipStr
       kp.level_pos = L.d_pipe;
       kp.pipe_dep = L.d_pipe + pl.pipe_pos.size();
       kp.level_begin = sg.off;
-      kp.chain_ticket = tickets + 4 * r + 2;
+      kp.chain_ticket = B.tickets + 4 * r + 2;
       bool n32 = false;
       if constexpr (sizeof(T) == 4) {
         n32 = pl.pipe_n32;
@@ -2556,69 +2513,67 @@ static int des_rounds(const DesLaunch &L, dev::DesK k, uint32_t *tickets, hipStr
       if (!n32) hipLaunchKernelGGL((des_down_pipe<T, false>), dim3(sg.cnt), dim3(kDownThreads), 0, stream, kp);
       piped_to = sg.r1 + 1;
     }
-    if (r < piped_to) goto finishes;
-    {
-    // 1. step begins (calls after calls)
-    const uint32_t na = pl.arr_off[r + 1] - pl.arr_off[r];
-    if (na) {
-      k.level_begin = pl.arr_off[r];
-      k.splits = splits_for(na);
-      hipLaunchKernelGGL(des_arrive<T>, dim3(k.splits, na), dim3(kDesUpThreads), 0, stream, k);
-    }
-    // 2. queues.  Zero-hold services: start = arrival.
-    const uint32_t nz = pl.zero_off[r + 1] - pl.zero_off[r];
-    if (nz) {
-      k.level_pos = L.d_zero_pos;
-      k.level_begin = pl.zero_off[r];
-      k.splits = splits_for(nz);
-      hipLaunchKernelGGL(des_zero<T>, dim3(k.splits, nz), dim3(kDesUpThreads), 0, stream, k);
-    }
-    //    Single-replica groups narrower than the chip take the
-    //    chained scan (many workgroups per position); wide groups and
-    //    replicated services one workgroup per position.
-    k.level_pos = L.d_fast_pos;
-    if (ISIM_DES_MIX) {
-      // single-replica positions (fused leaves or not): one launch
-      const uint32_t b = pl.fast_split[5 * r], e = pl.fast_split[5 * r + 2];
-      if (e > b) {
-        k.level_begin = b;
-        if (e - b < ISIM_DES_CHAIN_BELOW) {
-          k.chain_ticket = tickets + 4 * r;
-          hipLaunchKernelGGL(des_down_chain_mix<T>, dim3((e - b) * k.n_chunks), dim3(kDesThreads), 0, stream, k);
-        } else {
-          hipLaunchKernelGGL(des_down_mix<T>, dim3(e - b), dim3(kDownThreads), 0, stream, k);
+    if (r >= piped_to) {
+      // 1. step begins (calls after calls)
+      const uint32_t na = pl.arr_off[r + 1] - pl.arr_off[r];
+      if (na) {
+        k.level_begin = pl.arr_off[r];
+        k.splits = splits_for(na);
+        hipLaunchKernelGGL(des_arrive<T>, dim3(k.splits, na), dim3(kDesUpThreads), 0, stream, k);
+      }
+      // 2. queues.  Zero-hold services: start = arrival.
+      const uint32_t nz = pl.zero_off[r + 1] - pl.zero_off[r];
+      if (nz) {
+        k.level_pos = L.d_zero_pos;
+        k.level_begin = pl.zero_off[r];
+        k.splits = splits_for(nz);
+        hipLaunchKernelGGL(des_zero<T>, dim3(k.splits, nz), dim3(kDesUpThreads), 0, stream, k);
+      }
+      //    Single-replica groups narrower than the chip take the
+      //    chained scan (many workgroups per position); wide groups and
+      //    replicated services one workgroup per position.
+      k.level_pos = L.d_fast_pos;
+      if (ISIM_DES_MIX) {
+        // single-replica positions (fused leaves or not): one launch
+        const uint32_t b = pl.fast_split[5 * r], e = pl.fast_split[5 * r + 2];
+        if (e > b) {
+          k.level_begin = b;
+          if (e - b < ISIM_DES_CHAIN_BELOW) {
+            k.chain_ticket = B.tickets + 4 * r;
+            hipLaunchKernelGGL(des_down_chain_mix<T>, dim3((e - b) * k.n_chunks), dim3(kDesThreads), 0, stream, k);
+          } else {
+            hipLaunchKernelGGL(des_down_mix<T>, dim3(e - b), dim3(kDownThreads), 0, stream, k);
+          }
         }
       }
-    }
-    for (uint32_t j = ISIM_DES_MIX ? 2 : 0; j < 4; ++j) {
-      const uint32_t b = pl.fast_split[5 * r + j], e = pl.fast_split[5 * r + j + 1];
-      if (e == b) continue;
-      k.level_begin = b;
-      if (j < 2 && e - b < ISIM_DES_CHAIN_BELOW) {
-        k.chain_ticket = tickets + 4 * r + j;
-        hipLaunchKernelGGL(chain[j], dim3((e - b) * k.n_chunks), dim3(kDesThreads), 0, stream, k);
-      } else {
-        hipLaunchKernelGGL(down[j], dim3(e - b), dim3(kDownThreads), 0, stream, k);
+      for (uint32_t j = ISIM_DES_MIX ? 2 : 0; j < 4; ++j) {
+        const uint32_t b = pl.fast_split[5 * r + j], e = pl.fast_split[5 * r + j + 1];
+        if (e == b) continue;
+        k.level_begin = b;
+        if (j < 2 && e - b < ISIM_DES_CHAIN_BELOW) {
+          k.chain_ticket = B.tickets + 4 * r + j;
+          hipLaunchKernelGGL(chain[j], dim3((e - b) * k.n_chunks), dim3(kDesThreads), 0, stream, k);
+        } else {
+          hipLaunchKernelGGL(down[j], dim3(e - b), dim3(kDownThreads), 0, stream, k);
+        }
+      }
+      for (uint32_t si = pl.sorted_off[r]; si < pl.sorted_off[r + 1]; ++si) {
+        k.svc = pl.sorted[si];
+        const uint64_t m = (uint64_t)k.svc.pos_cnt * L.n_traces;
+        k.keys = B.keys_a;
+        k.vals = B.vals_a;
+        uint64_t g = (m + kDesUpThreads - 1) / kDesUpThreads;
+        g = g < 4096 ? g : 4096;
+        hipLaunchKernelGGL(des_sort_keys<T>, dim3((uint32_t)g), dim3(kDesUpThreads), 0, stream, k);
+        size_t tb = sort_tmp_bytes;
+        if (rocprim::radix_sort_pairs(B.sort_tmp, tb, B.keys_a, B.keys_b, B.vals_a, B.vals_b, (size_t)m, 0, 64,
+                                      stream) != hipSuccess)
+          return 1;
+        k.skeys = B.keys_b;
+        k.svals = B.vals_b;
+        hipLaunchKernelGGL(des_down_sorted<T>, dim3(1), dim3(kDesThreads), 0, stream, k);
       }
     }
-    for (uint32_t si = pl.sorted_off[r]; si < pl.sorted_off[r + 1]; ++si) {
-      k.svc = pl.sorted[si];
-      const uint64_t m = (uint64_t)k.svc.pos_cnt * L.n_traces;
-      k.keys = keys_a;
-      k.vals = vals_a;
-      uint64_t g = (m + kDesUpThreads - 1) / kDesUpThreads;
-      g = g < 4096 ? g : 4096;
-      hipLaunchKernelGGL(des_sort_keys<T>, dim3((uint32_t)g), dim3(kDesUpThreads), 0, stream, k);
-      size_t tb = sort_tmp_bytes;
-      if (rocprim::radix_sort_pairs(sort_tmp, tb, keys_a, keys_b, vals_a, vals_b, (size_t)m, 0, 64, stream) !=
-          hipSuccess)
-        return 1;
-      k.skeys = keys_b;
-      k.svals = vals_b;
-      hipLaunchKernelGGL(des_down_sorted<T>, dim3(1), dim3(kDesThreads), 0, stream, k);
-    }
-    }
-  finishes:
     // 3. finishes, deepest group first
     k.level_pos = L.d_fin_pos;
     for (uint32_t gi = pl.fin_round_off[r]; gi < pl.fin_round_off[r + 1]; ++gi) {
@@ -2639,8 +2594,6 @@ static int des_rounds(const DesLaunch &L, dev::DesK k, uint32_t *tickets, hipStr
 // Host launcher: the whole DES of one batch on `stream` (no allocation; no
 // host synchronisation unless the schedule is cyclic: its fixed-point passes
 // read one flag per pass).
-constexpr uint32_t kMaxPasses = 256;
-
 static std::atomic<uint32_t> g_spin_limit{kDesSpinLimit};
 uint32_t des_spin_limit() { return g_spin_limit.load(std::memory_order_relaxed); }
 void des_set_spin_limit(uint32_t polls) { g_spin_limit.store(polls, std::memory_order_relaxed); }
@@ -2656,23 +2609,24 @@ int des_launch(const DesLaunch &L, void *stream_) {
   k.steps = (const DesStep *)L.d_steps;
   k.child = L.d_child;
   k.arr_ops = L.d_arr_ops;
-  k.W = L.W;
-  k.WF = L.WF;
-  k.BK = L.BK;
-  k.A = L.A;
-  k.E = L.E;
-  k.blk = L.blk;
-  k.ovf = L.ovf;
+  const DesBufs &B = L.ws;
+  k.W = B.W;
+  k.WF = B.WF;
+  k.BK = B.BK;
+  k.A = B.A;
+  k.E = B.E;
+  k.blk = B.blk;
+  k.ovf = B.ovf;
   k.spin_limit = des_spin_limit();
-  k.stbits = L.stbits;
-  k.st_wpr = (uint32_t)status_wpr(L.n_traces);
+  k.stbits = B.stbits;
+  k.st_wpr = (uint32_t)des_status_wpr(L.n_traces);
   // statistics go to the staging copy, merged by des_commit unless the batch
   // is dropped (a 32-bit row overflowed, or no fixed point)
-  k.stats = L.stage;
-  k.table = L.stage + L.stats_words;
+  k.stats = B.stage;
+  k.table = B.stage + L.stats_words;
   k.records = L.d_records;
   k.N = L.n_traces;
-  k.ld = row_ld(L.n_traces);
+  k.ld = des_row_ld(L.n_traces);
   k.trace_begin = L.trace_begin;
   k.mean_ns = L.mean_ns;
   k.k0 = (uint32_t)L.seed;
@@ -2682,14 +2636,11 @@ int des_launch(const DesLaunch &L, void *stream_) {
   k.modeb = L.modeb;
   k.n_blk = (uint32_t)((L.n_traces + kDesChunk - 1) / kDesChunk);
   k.n_chunks = (uint32_t)((L.n_traces + kDownChunk - 1) / kDownChunk);
-  const uint64_t tk_bytes = al256(chain_tickets(*L.plan) * 4);
-  uint32_t *tickets = (uint32_t *)L.chain;
-  k.prog = (uint32_t *)((char *)L.chain + tk_bytes);
-  k.chain = (ChainState *)((char *)L.chain + tk_bytes + al256((uint64_t)L.n_pos * 4));
-  const uint64_t chain_bytes = des_chain_bytes(*L.plan, L.n_traces);
-  if (hipMemsetAsync(L.E, 0, L.n_traces * sizeof(uint32_t), stream) != hipSuccess) return 1;
-  if (hipMemsetAsync(L.ovf, 0, 8, stream) != hipSuccess) return 1;  // overflow flag + changed flag
-  if (hipMemsetAsync(L.stage, 0, (L.stats_words + table_words) * 8, stream) != hipSuccess) return 1;
+  k.prog = B.prog;
+  k.chain = B.chain;
+  if (hipMemsetAsync(B.E, 0, L.n_traces * sizeof(uint32_t), stream) != hipSuccess) return 1;
+  if (hipMemsetAsync(B.ovf, 0, 8, stream) != hipSuccess) return 1;  // overflow flag + changed flag
+  if (hipMemsetAsync(B.stage, 0, (L.stats_words + table_words) * 8, stream) != hipSuccess) return 1;
   hipLaunchKernelGGL(des_arrivals, dim3(k.n_blk), dim3(kDesThreads), 0, stream, k);
   hipLaunchKernelGGL(des_scan_blocks, dim3(1), dim3(kDesThreads), 0, stream, k);
   hipLaunchKernelGGL(des_add_blocks, dim3(k.n_blk), dim3(kDesThreads), 0, stream, k);
@@ -2698,21 +2649,21 @@ int des_launch(const DesLaunch &L, void *stream_) {
     hipLaunchKernelGGL(des_status, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, k);
   }
   auto pass = [&](const DesK &kk) -> int {
-    if (hipMemsetAsync(L.chain, 0, chain_bytes, stream) != hipSuccess) return 1;
-    return narrow ? des_rounds<uint32_t>(L, kk, tickets, stream) : des_rounds<uint64_t>(L, kk, tickets, stream);
+    if (hipMemsetAsync(B.tickets, 0, B.pass_zero_bytes, stream) != hipSuccess) return 1;
+    return narrow ? des_rounds<uint32_t>(L, kk, stream) : des_rounds<uint64_t>(L, kk, stream);
   };
   if (L.plan->cyclic) {
     // fixed point: back-edge rows start at 0 (a lower bound of every
     // relative time); quiet passes until no stored value changes, then the
     // pass that records the statistics
     const uint64_t rb = narrow ? 4 : 8;
-    if (hipMemsetAsync(L.W, 0, (uint64_t)L.n_pos * k.ld * rb, stream) != hipSuccess ||
-        hipMemsetAsync(L.WF, 0, (uint64_t)L.n_pos * k.ld * rb, stream) != hipSuccess ||
-        hipMemsetAsync(L.BK, 0, (uint64_t)L.plan->steps.size() * k.ld * rb, stream) != hipSuccess)
+    if (hipMemsetAsync(B.W, 0, (uint64_t)L.n_pos * k.ld * rb, stream) != hipSuccess ||
+        hipMemsetAsync(B.WF, 0, (uint64_t)L.n_pos * k.ld * rb, stream) != hipSuccess ||
+        hipMemsetAsync(B.BK, 0, (uint64_t)L.plan->steps.size() * k.ld * rb, stream) != hipSuccess)
       return 1;
     DesK kq = k;
     kq.quiet = 1;
-    kq.changed = L.ovf + 1;
+    kq.changed = B.changed;
     uint32_t p = 0;
     for (; p < kMaxPasses; ++p) {
       if (hipMemsetAsync(kq.changed, 0, 4, stream) != hipSuccess) return 1;
@@ -2725,7 +2676,7 @@ int des_launch(const DesLaunch &L, void *stream_) {
     }
     if (p == kMaxPasses) {
       static const uint32_t no_fixed_point = 2;
-      if (hipMemcpyAsync(L.ovf, &no_fixed_point, 4, hipMemcpyHostToDevice, stream) != hipSuccess ||
+      if (hipMemcpyAsync(B.ovf, &no_fixed_point, 4, hipMemcpyHostToDevice, stream) != hipSuccess ||
           hipStreamSynchronize(stream) != hipSuccess)
         return 1;
     }
@@ -2748,8 +2699,8 @@ int des_launch(const DesLaunch &L, void *stream_) {
   }
   uint64_t g = (L.stats_words + table_words + 255) / 256;
   g = g < 1024 ? g : 1024;
-  hipLaunchKernelGGL(des_commit, dim3((uint32_t)(g ? g : 1)), dim3(256), 0, stream, L.stage, L.d_stats, L.d_table,
-                     L.stats_words, table_words, (const uint32_t *)L.ovf);
+  hipLaunchKernelGGL(des_commit, dim3((uint32_t)(g ? g : 1)), dim3(256), 0, stream, B.stage, L.d_stats, L.d_table,
+                     L.stats_words, table_words, (const uint32_t *)B.ovf);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

@@ -53,7 +53,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 #include <rocprim/device/device_scan_by_key.hpp>
 
-#include "des.h"
+#include "des_layout.h"
 #include "kernel_abi.h"
 #include "tree_walk.h"
 
@@ -544,11 +544,7 @@ __global__ void __launch_bounds__(kT) k_steps(K k, const unsigned long long *ops
   }
 }
 
-// FIFO of one worker as a max-plus map x -> max(x + B, C) on "free at x"
-// (des.hip SegMP without the segment flag: rocPRIM's scan by key segments)
-struct MP {
-  uint64_t B, C;
-};
+// composition of two workers' max-plus maps (MP: des_layout.h)
 struct MPThen {
   __device__ __forceinline__ MP operator()(const MP &a, const MP &b) const {
     const uint64_t c = a.C + b.B;
@@ -943,11 +939,7 @@ __global__ void __launch_bounds__(kT) k_qout(K k, uint64_t m, const uint32_t *rk
 // decoupled look-back (des.hip chain_body's hand-off: sc1 stores drained
 // before the flag store, sc1 loads).  The flag word carries the launch's
 // epoch, so the states are cleared once per batch, not per launch.
-struct QState {
-  uint64_t agg, inc;  // the max after the tile's last segment start (flag >= 1); with the prefix (flag 2)
-  uint32_t flag, pad[3];
-};
-static_assert(sizeof(QState) == 32, "QState is 32 bytes");
+// (QState, one per tile: des_layout.h)
 constexpr uint32_t kQAgg = 1, kQInc = 2, kQEpochShift = 2;
 constexpr int64_t kQMin = INT64_MIN;
 __device__ __forceinline__ int64_t qmax(int64_t a, int64_t b) { return a > b ? a : b; }
@@ -1411,9 +1403,10 @@ __global__ void k_flag_retry(unsigned long long *stats, const uint32_t *ovf) {
 
 namespace {
 
-uint64_t al256(uint64_t b) { return (b + 255) & ~255ull; }
+using namespace dit;
+
 uint32_t grid_for(uint64_t m, uint32_t cap = 8192) {
-  const uint64_t g = (m + dit::kT - 1) / dit::kT;
+  const uint64_t g = (m + kT - 1) / kT;
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
 }
 uint32_t bits_for(uint64_t v) {  // bits of the largest key v
@@ -1428,618 +1421,554 @@ size_t scan_u64_bytes(uint64_t n) {
   return b;
 }
 constexpr uint32_t kPrewalkBlocks = 2048;  // pre-walk grid (waves refill from a global batch counter)
-constexpr uint32_t kMaxPasses = 256;       // fixed-point passes of a cyclic schedule (des.hip)
 // incremental quiet passes: chunks of 256 traces, or larger so that a chunk
 // id fits 16 bits (step ops and kept orders carry it)
 uint32_t chunk_shift(uint64_t n) { return std::max<uint32_t>(8u, bits_for(n) > 16u ? bits_for(n) - 16u : 0u); }
 
-}  // namespace
-
-// per trace: gaps, arrivals, hops, item ends (u64), status_err (u32), scan temp
-uint64_t des_items_workspace_bytes(uint64_t n) {
-  return 4 * al256(n * 8) + al256(n * 4) + al256(16) + al256(scan_u64_bytes(n)) + 256;
+// The pre-walk variant: register frames (8 + spill, 16, 8), time width, error
+// mode (mode B walks draw errors), where the nodes are read (a wide tree's
+// 16-byte nodes, LDS, global memory), counting or emitting.
+using PrewalkFn = void (*)(K, unsigned long long *);
+enum PrewalkNodes : uint32_t { kNodesWide = 0, kNodesLds = 1, kNodesGlobal = 2 };
+template <int FR, bool SP, bool T6, bool MB>
+PrewalkFn prewalk_variant(PrewalkNodes nodes, bool emit) {
+  static const PrewalkFn v[3][2] = {
+      {k_prewalk<FR, SP, false, false, T6, MB, true>, k_prewalk<FR, SP, true, false, T6, MB, true>},
+      {k_prewalk<FR, SP, false, true, T6, MB>, k_prewalk<FR, SP, true, true, T6, MB>},
+      {k_prewalk<FR, SP, false, false, T6, MB>, k_prewalk<FR, SP, true, false, T6, MB>}};
+  return v[nodes][emit];
+}
+PrewalkFn prewalk_kernel(uint32_t frames, bool t64, bool modeb, PrewalkNodes nodes, bool emit) {
+  // [frames: 8 + spill, 16, 8][t64][mode B]
+  static PrewalkFn (*const pick[3][2][2])(PrewalkNodes, bool) = {
+      {{prewalk_variant<8, true, false, false>, prewalk_variant<8, true, false, true>},
+       {prewalk_variant<8, true, true, false>, prewalk_variant<8, true, true, true>}},
+      {{prewalk_variant<16, false, false, false>, prewalk_variant<16, false, false, true>},
+       {prewalk_variant<16, false, true, false>, prewalk_variant<16, false, true, true>}},
+      {{prewalk_variant<8, false, false, false>, prewalk_variant<8, false, false, true>},
+       {prewalk_variant<8, false, true, false>, prewalk_variant<8, false, true, true>}}};
+  return pick[frames > 16 ? 0 : frames > 8 ? 1 : 2][t64][modeb](nodes, emit);
 }
 
-int des_items_launch(const DesItemsLaunch &L, void *stream_, std::string &err) {
-  using namespace dit;
-  hipStream_t s = (hipStream_t)stream_;
-  const DesPlan &pl = *L.plan;
-  const uint64_t n = L.n_traces;
-  char *ws = (char *)L.workspace;
-  auto take = [&](uint64_t bytes) {
-    char *p = ws;
-    ws += al256(bytes);
-    return (void *)p;
-  };
-  K k{};
-  k.pos = (const DesPos *)L.d_pos;
-  k.ip = (const DesItemPos *)L.d_item_pos;
-  k.steps = (const DesStep *)L.d_steps;
-  k.step_round = L.d_step_round;
-  k.nodes = (const unsigned long long *)L.d_nodes;
-  k.ext = (const TreeExt *)L.d_ext;
-  k.tstep = (const TreeStep *)L.d_tstep;
-  k.gap = (uint64_t *)take(n * 8);
-  k.A = (uint64_t *)take(n * 8);
-  k.cnt = (uint64_t *)take(n * 8);
-  k.tend = (uint64_t *)take(n * 8);
-  k.terr = (uint32_t *)take(n * 4);
-  // the refill counters of the two pre-walks
-  unsigned long long *work = (unsigned long long *)take(16);
-  const size_t scan_bytes = scan_u64_bytes(n);
-  void *scan_tmp = take(scan_bytes);
-  k.stats = (unsigned long long *)L.d_stats;
-  k.table = (unsigned long long *)L.d_table;
-  k.records = L.d_records;
-  k.n = n;
-  k.trace_begin = L.trace_begin;
-  k.mean_ns = L.mean_ns;
-  k.k0 = (uint32_t)L.seed;
-  k.k1 = (uint32_t)(L.seed >> 32);
-  k.n_slots = L.n_slots;
-  k.modeb = pl.modeb ? 1u : 0u;
-  uint32_t max_reps = 1, max_row = 0;
-  for (const DesPos &q : pl.pos) {
-    max_reps = std::max(max_reps, q.reps);
-    max_row = std::max(max_row, q.row);
+// per-batch buffers come from the handler's private pool (DesItemsLaunch::pool:
+// never the device's default pool, whose attributes belong to the application)
+// and go back to it on every return
+struct PoolBuf {
+  void *p = nullptr;
+  hipStream_t s;
+  ~PoolBuf() {
+    if (p) (void)hipFreeAsync(p, s);
   }
-  const uint32_t rep_bits = max_reps > 1 ? bits_for(max_reps - 1) : 0u;
-  k.aw = pl.item_acc;
-  k.bw = pl.item_bk;
-  auto fail = [&](const char *what) {
+};
+
+// One batch: the stages of the file's header comment in stream order.  Every
+// stage returns 0, or the launcher's return code with the reason in `err`.
+struct Batch {
+  const DesItemsLaunch &L;
+  const DesPlan &pl;
+  hipStream_t s;
+  std::string &err;
+  const uint64_t n;
+  const uint32_t R, G;  // rounds, finish groups
+  K k{};
+  ItemTraceBufs T{};
+  ItemBufs B{};
+  PoolBuf spill_mem, item_mem;
+  DesItemsReport rep{};  // isim_des_last_batch: host synchronisations, passes, items
+  size_t scan_bytes = 0, tmp_bytes = 0;
+  ItemDims dims{};
+  uint64_t M = 0;
+  std::vector<uint64_t> row_hold;  // per duration-table row: the service's worker hold
+  uint32_t rep_bits = 0, row_bits = 0;
+  bool qscan = false, two_sorts = false, keep_ord = false;
+  uint32_t qepoch = 0, qtbase = 0;  // k_qscan launches (the states' epochs: 1, 2, ...) and tickets taken
+  uint32_t qn = 0;                  // k_qarr launches: the arrival-range slot alternates
+  std::vector<uint32_t> qoff, foff, soff;  // item ranges of the rounds' queues, finish groups, step ops
+  std::vector<uint8_t> have_ord;           // per sort round: an order is kept
+  std::vector<uint64_t> rlo, rhi;          // per sort round: its arrival range over the passes
+
+  Batch(const DesItemsLaunch &L_, hipStream_t s_, std::string &err_)
+      : L(L_), pl(*L_.plan), s(s_), err(err_), n(L_.n_traces), R(pl.rounds()), G((uint32_t)pl.fin_off.size() - 1),
+        spill_mem{nullptr, s_}, item_mem{nullptr, s_} {}
+  ~Batch() {
+    if (L.report) *L.report = rep;
+  }
+  int fail(const char *what) {
     err = std::string("DES items: ") + what;
     return 1;
-  };
-  // the batch's report (isim_des_last_batch): host synchronisations, passes, items
-  DesItemsReport rep{};
-  auto sync_s = [&]() {
+  }
+  hipError_t sync_s() {
     ++rep.syncs;
     return hipStreamSynchronize(s);
-  };
-  struct ReportOut {
-    const DesItemsReport &r;
-    DesItemsReport *out;
-    ~ReportOut() {
-      if (out) *out = r;
-    }
-  } report_out{rep, L.report};
-  // 1. arrivals
-  hipLaunchKernelGGL(k_gaps, dim3(grid_for(n)), dim3(kT), 0, s, k);
-  size_t b = scan_bytes;
-  if (rocprim::inclusive_scan(scan_tmp, b, k.gap, k.A, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess)
-    return fail("arrival scan");
-  // 2. pre-walk: count, offsets, emit
-  const uint32_t fr = L.tree_frames;
-  const bool spill = fr > 16;
-  // per-batch buffers come from the handler's private pool (L.pool: never the
-  // device's default pool, whose attributes belong to the application) and go
-  // back to it on every return
-  struct PoolBuf {
-    void *p = nullptr;
-    hipStream_t s;
-    ~PoolBuf() {
-      if (p) (void)hipFreeAsync(p, s);
-    }
-  } spill_mem{nullptr, s}, item_mem{nullptr, s};
-  auto pool_alloc = [&](PoolBuf &b, uint64_t bytes) {
-    return hipMallocFromPoolAsync(&b.p, bytes, (hipMemPool_t)L.pool, s) == hipSuccess;
-  };
-  uint32_t *spill_buf = nullptr;
-  const uint64_t pw_threads = (uint64_t)kPrewalkBlocks * kT;
-  if (spill) {
-    const uint64_t words = (uint64_t)(fr - 8 + 1) *
-                           ((L.tree_t64 ? kTreeSpillWords64 : kTreeSpillWords) + (L.tree_wide ? kTreeSpillWide : 0u)) *
-                           pw_threads;
-    if (!pool_alloc(spill_mem, words * 4)) return fail("spill allocation");
-    spill_buf = (uint32_t *)spill_mem.p;
   }
-  k.spill = spill_buf;
-  // the nodes in LDS (1024-thread workgroups, one per CU at these register
-  // counts) when they fit in 96 KB
-  k.n_nodes = L.n_nodes;
-  const uint32_t lds_nodes = L.n_nodes * 8u;
-  const bool ldsn = !L.tree_wide && lds_nodes <= 96u * 1024u ;
-  auto launch = [&](auto kern, unsigned long long *w) {
+  bool pool_alloc(PoolBuf &b, uint64_t bytes) {
+    return hipMallocFromPoolAsync(&b.p, bytes, (hipMemPool_t)L.pool, s) == hipSuccess;
+  }
+
+  int run() {
+    setup();
+    if (int rc = arrivals()) return rc;
+    if (int rc = count_items()) return rc;
+    if (int rc = allocate()) return rc;
+    if (int rc = emit_items()) return rc;
+    if (int rc = renumber()) return rc;
+    if (int rc = buckets()) return rc;
+    if (int rc = fixed_point()) return rc;
+    return finalize();
+  }
+
+  void setup() {
+    Arena ws(L.workspace);
+    scan_bytes = scan_u64_bytes(n);
+    des_items_trace_layout(ws, T, n, scan_bytes);
+    k.pos = (const DesPos *)L.d_pos;
+    k.ip = (const DesItemPos *)L.d_item_pos;
+    k.steps = (const DesStep *)L.d_steps;
+    k.step_round = L.d_step_round;
+    k.nodes = (const unsigned long long *)L.d_nodes;
+    k.ext = (const TreeExt *)L.d_ext;
+    k.tstep = (const TreeStep *)L.d_tstep;
+    k.n_nodes = L.n_nodes;
+    k.gap = T.gap;
+    k.A = T.A;
+    k.cnt = T.cnt;
+    k.tend = T.tend;
+    k.terr = T.terr;
+    k.stats = (unsigned long long *)L.d_stats;
+    k.table = (unsigned long long *)L.d_table;
+    k.records = L.d_records;
+    k.n = n;
+    k.trace_begin = L.trace_begin;
+    k.mean_ns = L.mean_ns;
+    k.k0 = (uint32_t)L.seed;
+    k.k1 = (uint32_t)(L.seed >> 32);
+    k.n_slots = L.n_slots;
+    k.modeb = pl.modeb ? 1u : 0u;
+    k.aw = pl.item_acc;
+    k.bw = pl.item_bk;
+    k.cshift = chunk_shift(n);
+    k.spin_limit = des_spin_limit();
+    uint32_t max_reps = 1, max_row = 0;
+    for (const DesPos &q : pl.pos) {
+      max_reps = std::max(max_reps, q.reps);
+      max_row = std::max(max_row, q.row);
+    }
+    rep_bits = max_reps > 1 ? bits_for(max_reps - 1) : 0u;
+    row_bits = bits_for(max_row);
+    row_hold.assign((size_t)max_row + 1, 0);
+    for (const DesPos &q : pl.pos) row_hold[q.row] = q.hold;
+    // ISIM_FLAG_DES_TWO_SORTS: always the two-sort queue path; ISIM_FLAG_DES_SORT_ALL:
+    // never reuse a kept order (independent checks)
+    two_sorts = (L.flags & ISIM_FLAG_DES_TWO_SORTS) != 0;
+    keep_ord = pl.cyclic && !(L.flags & ISIM_FLAG_DES_SORT_ALL);
+    have_ord.assign(R, 0);
+    rlo.assign(R, ~0ull);
+    rhi.assign(R, 0);
+  }
+
+  // 1. arrivals
+  int arrivals() {
+    hipLaunchKernelGGL(k_gaps, dim3(grid_for(n)), dim3(kT), 0, s, k);
+    size_t b = scan_bytes;
+    if (rocprim::inclusive_scan(T.scan_tmp, b, k.gap, k.A, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess)
+      return fail("arrival scan");
+    return 0;
+  }
+
+  // 2. the pre-walk, counting or emitting.  The nodes in LDS (1024-thread
+  // workgroups, one per CU at these register counts) when they fit in 96 KB
+  void prewalk(bool emit) {
+    const uint32_t lds_nodes = L.n_nodes * 8u;
+    const bool ldsn = !L.tree_wide && lds_nodes <= 96u * 1024u;
+    const PrewalkFn kern = prewalk_kernel(L.tree_frames, L.tree_t64 != 0, pl.modeb,
+                                          L.tree_wide ? kNodesWide : ldsn ? kNodesLds : kNodesGlobal, emit);
+    unsigned long long *w = T.work + (emit ? 1 : 0);
     if (ldsn) {
       (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_nodes);
       hipLaunchKernelGGL(kern, dim3(kPrewalkBlocks / 4), dim3(1024), lds_nodes, s, k, w);
     } else {
       hipLaunchKernelGGL(kern, dim3(kPrewalkBlocks), dim3(kT), 0, s, k, w);
     }
-  };
-  // the variant: register frames (8 + spill, 16, 8), nodes in LDS, time width
-  // (and the error mode: mode B walks draw errors)
-  auto pw = [&](auto fr_c, auto spill_c, auto t64_c, auto mb_c, bool emit) {
-    constexpr int FRc = decltype(fr_c)::value;
-    constexpr bool SP = decltype(spill_c)::value, T6 = decltype(t64_c)::value, MB = decltype(mb_c)::value;
-    unsigned long long *w = work + (emit ? 1 : 0);
-    if (L.tree_wide) {
-      if (emit) launch(k_prewalk<FRc, SP, true, false, T6, MB, true>, w);
-      else launch(k_prewalk<FRc, SP, false, false, T6, MB, true>, w);
-    } else if (ldsn) {
-      if (emit) launch(k_prewalk<FRc, SP, true, true, T6, MB>, w);
-      else launch(k_prewalk<FRc, SP, false, true, T6, MB>, w);
-    } else {
-      if (emit) launch(k_prewalk<FRc, SP, true, false, T6, MB>, w);
-      else launch(k_prewalk<FRc, SP, false, false, T6, MB>, w);
-    }
-  };
-  auto prewalk_t = [&](auto t64_c, auto mb_c, bool emit) {
-    if (spill) pw(std::integral_constant<int, 8>{}, std::true_type{}, t64_c, mb_c, emit);
-    else if (fr > 8) pw(std::integral_constant<int, 16>{}, std::false_type{}, t64_c, mb_c, emit);
-    else pw(std::integral_constant<int, 8>{}, std::false_type{}, t64_c, mb_c, emit);
-  };
-  auto prewalk_m = [&](auto mb_c, bool emit) {
-    if (L.tree_t64) prewalk_t(std::true_type{}, mb_c, emit);
-    else prewalk_t(std::false_type{}, mb_c, emit);
-  };
-  auto prewalk = [&](bool emit) {
-    if (pl.modeb) prewalk_m(std::true_type{}, emit);
-    else prewalk_m(std::false_type{}, emit);
-  };
-  if (hipMemsetAsync(work, 0, 16, s) != hipSuccess) return fail("memset");
-  prewalk(false);
-  b = scan_bytes;
-  if (rocprim::inclusive_scan(scan_tmp, b, k.cnt, k.tend, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess)
-    return fail("item offset scan");
-  uint64_t M = 0;
-  if (hipMemcpyAsync(&M, k.tend + (n - 1), 8, hipMemcpyDeviceToHost, s) != hipSuccess || sync_s() != hipSuccess)
-    return fail("item count read-back");
-  if (M >= 0xFFFFFFFFull) {
-    err = "DES items: a batch of more than 2^32 - 1 executed invocations (use smaller batches)";
-    return 2;
   }
-  k.M = M;
-  rep.items = M;
-  rep.passes = 1;
-  // the per-item arrays and the rounds' sort buffers, one allocation
-  const uint32_t R = pl.rounds();
-  const uint32_t G = (uint32_t)pl.fin_off.size() - 1;
-  size_t sort32_bytes = 0, sort64_bytes = 0, sbk_bytes = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, sort32_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                                  (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)M, 0, 32);
-  (void)rocprim::radix_sort_pairs(nullptr, sort64_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr,
-                                  (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)M, 0, 64);
-  (void)rocprim::inclusive_scan_by_key(nullptr, sbk_bytes, (const uint32_t *)nullptr, (const MP *)nullptr,
-                                       (MP *)nullptr, (size_t)M, MPThen(), rocprim::equal_to<uint32_t>());
-  size_t sop_bytes = 0;
-  if (pl.item_bk)
-    (void)rocprim::radix_sort_pairs(nullptr, sop_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                                    (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                    (size_t)(M * pl.item_bk), 0, 32);
-  size_t perm_bytes = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, perm_bytes, rocprim::make_transform_iterator((const uint4 *)nullptr, PosOf()),
-                                  (uint32_t *)nullptr, rocprim::make_counting_iterator<uint32_t>(0u),
-                                  (uint32_t *)nullptr, (size_t)M, 0, 32);
-  const size_t tmp_bytes =
-      std::max({sort32_bytes, sort64_bytes, sbk_bytes, sop_bytes, perm_bytes});
-  // per duration-table row: the service's worker hold (the queue kernels read no item's position)
-  std::vector<uint64_t> row_hold(std::max<size_t>(1, max_row + 1), 0);
-  for (const DesPos &q : pl.pos) row_hold[q.row] = q.hold;
-  const size_t rows_n = row_hold.size();
-  const uint64_t parts[] = {
-      M * 4, M * 4, M * 4, M,                                  // ipos ipar itr iown
-      M * 8, M * 8, M * 8,                                     // IA IS IF
-      M * 8 * k.aw, M * 8 * std::max<uint32_t>(1, k.bw),       // acc bk
-      pl.cyclic ? M * 8 * k.aw : 8,                            // acc of the previous pass
-      k.bw ? M * k.bw * 4 : 4, k.bw ? M * k.bw * 8 : 8,        // step ops: rounds, (item, step)
-      4, pl.cyclic ? M * 4 : 4, 4, 4, M * 4, M * 4,            // (spare) ord (spare spare) qids fids
-      M * 8, M * 8, M * 4, M * 4,                              // round: key a/b, val a/b
-      M * 4, M * 4, M * 4, M * 4, M * 16, M * 16, M * 4,      // rk a/b, rv a/b, mp in/out, sid
-      4, 4, 16,                                                // (k_qscan ticket, spare); ovf: key overflow, no fixed
-                                                               // point, look-back fault, step-op count
-      96,                                                      // two arrival-range slots; change flag, count
-      k.bw ? M * k.bw * 4 : 4, k.bw ? M * k.bw * 8 : 8,        // step ops sorted
-      (uint64_t)(R + 1) * 4, (uint64_t)rows_n * 8,              // step-op offsets; hold per row
-      M * 4, n * 4, M * 16, 4, 4, 8, M * 4,                    // ihop troot; erec (3 spare); inverse
-      (uint64_t)(pl.pos.size() + 1) * 4, (uint64_t)pl.pos.size() * 4, (uint64_t)pl.pos.size() * 4,  // poff qdst fdst
-      tmp_bytes,
-      M * 2, (n >> chunk_shift(n)) + 1, (n >> chunk_shift(n)) + 1,  // replicas; the two chunk-change maps
-      pl.cyclic ? M * 2 : 2,                                    // kept orders' trace chunks
-      pl.modeb ? M * 4 : 4,                                     // mode B: failed call step per item
-      n + 1, n + 1};                                            // the two per-trace change maps
-  uint64_t total = 0;
-  for (uint64_t q : parts) total += al256(q ? q : 1);
-  if (!pool_alloc(item_mem, total)) return fail("item allocation");
-  char *at = (char *)item_mem.p;
-  auto carve = [&](uint64_t bytes) {
-    char *p = at;
-    at += al256(bytes ? bytes : 1);
-    return (void *)p;
-  };
-  k.ipos = (uint32_t *)carve(parts[0]);
-  k.ipar = (uint32_t *)carve(parts[1]);
-  k.itr = (uint32_t *)carve(parts[2]);
-  k.iown = (uint8_t *)carve(parts[3]);
-  k.IA = (uint64_t *)carve(parts[4]);
-  k.IS = (uint64_t *)carve(parts[5]);
-  k.IF = (uint64_t *)carve(parts[6]);
-  k.acc = (uint64_t *)carve(parts[7]);
-  k.bk = (uint64_t *)carve(parts[8]);
-  uint64_t *acc_b = (uint64_t *)carve(parts[9]);
-  uint32_t *op_k = (uint32_t *)carve(parts[10]);
-  unsigned long long *op_v = (unsigned long long *)carve(parts[11]);
-  (void)carve(parts[12]);
-  uint32_t *ord = (uint32_t *)carve(parts[13]);  // per sort round: the last sorted order (list indices)
-  (void)carve(parts[14]);
-  (void)carve(parts[15]);
-  uint32_t *qids = (uint32_t *)carve(parts[16]), *fids = (uint32_t *)carve(parts[17]);
-  uint64_t *key_a = (uint64_t *)carve(parts[18]), *key_b = (uint64_t *)carve(parts[19]);
-  uint32_t *val_a = (uint32_t *)carve(parts[20]), *val_b = (uint32_t *)carve(parts[21]);
-  uint32_t *rk_a = (uint32_t *)carve(parts[22]), *rk_b = (uint32_t *)carve(parts[23]);
-  uint32_t *rv_a = (uint32_t *)carve(parts[24]), *rv_b = (uint32_t *)carve(parts[25]);
-  MP *mp_in = (MP *)carve(parts[26]), *mp_out = (MP *)carve(parts[27]);
-  uint32_t *sid = (uint32_t *)carve(parts[28]);
-  uint32_t *qticket = (uint32_t *)carve(parts[29]);  // k_qscan's tile tickets (its states: mp_out)
-  (void)carve(parts[30]);
-  uint32_t *ovf = (uint32_t *)carve(parts[31]);
-  k.fault = ovf + 2;
-  k.spin_limit = des_spin_limit();
-  uint64_t *mm = (uint64_t *)carve(parts[32]);
-  uint32_t *chg = (uint32_t *)(mm + 8);  // [0] a quiet pass changed a value, [1] (spare)
-  uint32_t *op_k2 = (uint32_t *)carve(parts[33]);
-  unsigned long long *op_v2 = (unsigned long long *)carve(parts[34]);
-  uint32_t *d_soff = (uint32_t *)carve(parts[35]);
-  uint64_t *d_row_hold = (uint64_t *)carve(parts[36]);
-  k.ihop = (uint32_t *)carve(parts[37]);
-  k.troot = (uint32_t *)carve(parts[38]);
-  k.erec = (uint4 *)carve(parts[39]);
-  (void)carve(parts[40]);
-  (void)carve(parts[41]);
-  (void)carve(parts[42]);
-  uint32_t *inv = (uint32_t *)carve(parts[43]);
-  uint32_t *d_poff = (uint32_t *)carve(parts[44]);
-  uint32_t *d_qdst = (uint32_t *)carve(parts[45]);
-  uint32_t *d_fdst = (uint32_t *)carve(parts[46]);
-  void *tmp = carve(parts[47]);
-  k.irep = (uint16_t *)carve(parts[48]);
-  k.cshift = chunk_shift(n);
-  const uint64_t n_chunks = (n >> k.cshift) + 1;
-  uint8_t *chg_a = (uint8_t *)carve(parts[49]), *chg_b = (uint8_t *)carve(parts[50]);
-  uint16_t *ordc = (uint16_t *)carve(parts[51]);
-  uint32_t *ifst = (uint32_t *)carve(parts[52]);
-  k.ifst = pl.modeb ? ifst : nullptr;
-  uint8_t *chg_ta = (uint8_t *)carve(parts[53]), *chg_tb = (uint8_t *)carve(parts[54]);
-  // the rounds' queues by k_qscan (its keys a - j h need j h < 2^62), else
-  // rocPRIM's scan by key over the maps and k_qout (ISIM_FLAG_DES_SCAN_BY_KEY:
-  // always, an independent check of k_qscan)
-  uint64_t max_hold = 0;
-  for (uint64_t hv : row_hold) max_hold = std::max(max_hold, hv);
-  const bool qscan = !(L.flags & ISIM_FLAG_DES_SCAN_BY_KEY) &&
-                     (max_hold == 0 || M <= (1ull << 62) / max_hold);
-  QState *qstate = (QState *)mp_out;  // mp_out's bytes: >= 32 B per 512 items
-  uint32_t qepoch = 0, qtbase = 0;
-  int rc = 0;
-  std::vector<uint32_t> qoff(R + 1), foff(G + 1);
-  do {
+
+  // 2a. each trace's executed invocations, the item offsets, the batch's items
+  int count_items() {
+    const uint32_t fr = L.tree_frames;
+    if (fr > 16) {  // frames past the registers spill to global memory
+      const uint64_t words = (uint64_t)(fr - 8 + 1) *
+                             ((L.tree_t64 ? kTreeSpillWords64 : kTreeSpillWords) + (L.tree_wide ? kTreeSpillWide : 0u)) *
+                             kPrewalkBlocks * kT;
+      if (!pool_alloc(spill_mem, words * 4)) return fail("spill allocation");
+    }
+    k.spill = (uint32_t *)spill_mem.p;
+    if (hipMemsetAsync(T.work, 0, 16, s) != hipSuccess) return fail("memset");
+    prewalk(false);
+    size_t b = scan_bytes;
+    if (rocprim::inclusive_scan(T.scan_tmp, b, k.cnt, k.tend, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess)
+      return fail("item offset scan");
+    if (hipMemcpyAsync(&M, k.tend + (n - 1), 8, hipMemcpyDeviceToHost, s) != hipSuccess || sync_s() != hipSuccess)
+      return fail("item count read-back");
+    if (M >= 0xFFFFFFFFull) {
+      err = "DES items: a batch of more than 2^32 - 1 executed invocations (use smaller batches)";
+      return 2;
+    }
+    k.M = M;
+    rep.items = M;
+    rep.passes = 1;
+    return 0;
+  }
+
+  // the per-item arrays and the rounds' sort buffers, one allocation (des_items_layout)
+  int allocate() {
+    size_t sort32_bytes = 0, sort64_bytes = 0, sbk_bytes = 0, sop_bytes = 0, perm_bytes = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, sort32_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                    (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)M, 0, 32);
+    (void)rocprim::radix_sort_pairs(nullptr, sort64_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr,
+                                    (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)M, 0, 64);
+    (void)rocprim::inclusive_scan_by_key(nullptr, sbk_bytes, (const uint32_t *)nullptr, (const MP *)nullptr,
+                                         (MP *)nullptr, (size_t)M, MPThen(), rocprim::equal_to<uint32_t>());
+    if (pl.item_bk)
+      (void)rocprim::radix_sort_pairs(nullptr, sop_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                      (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                      (size_t)(M * pl.item_bk), 0, 32);
+    (void)rocprim::radix_sort_pairs(nullptr, perm_bytes,
+                                    rocprim::make_transform_iterator((const uint4 *)nullptr, PosOf()),
+                                    (uint32_t *)nullptr, rocprim::make_counting_iterator<uint32_t>(0u),
+                                    (uint32_t *)nullptr, (size_t)M, 0, 32);
+    tmp_bytes = std::max({sort32_bytes, sort64_bytes, sbk_bytes, sop_bytes, perm_bytes});
+    dims = ItemDims{M, n, k.aw, k.bw, R, row_hold.size(), pl.pos.size(), pl.cyclic, pl.modeb, tmp_bytes, k.cshift};
+    Arena sizing;
+    des_items_layout(sizing, B, dims);
+    if (!pool_alloc(item_mem, sizing.bytes())) return fail("item allocation");
+    Arena carving(item_mem.p);
+    des_items_layout(carving, B, dims);
+    k.ipos = B.ipos;
+    k.ipar = B.ipar;
+    k.itr = B.itr;
+    k.iown = B.iown;
+    k.IA = B.IA;
+    k.IS = B.IS;
+    k.IF = B.IF;
+    k.acc = B.acc;
+    k.bk = B.bk;
+    k.ihop = B.ihop;
+    k.troot = B.troot;
+    k.erec = (uint4 *)B.erec;
+    k.irep = B.irep;
+    k.ifst = pl.modeb ? B.ifst : nullptr;
+    k.fault = B.ovf + 2;
+    // the rounds' queues by k_qscan (its keys a - j h need j h < 2^62), else
+    // rocPRIM's scan by key over the maps and k_qout (ISIM_FLAG_DES_SCAN_BY_KEY:
+    // always, an independent check of k_qscan)
+    const uint64_t max_hold = *std::max_element(row_hold.begin(), row_hold.end());
+    qscan = !(L.flags & ISIM_FLAG_DES_SCAN_BY_KEY) && (max_hold == 0 || M <= (1ull << 62) / max_hold);
+    return 0;
+  }
+
+  // 2b. each item's position, caller and contention-free duration
+  int emit_items() {
     static const uint64_t mm_empty[8] = {~0ull, 0ull, 0ull, 0ull, ~0ull, 0ull, 0ull, 0ull};
-    if (hipMemsetAsync(ovf, 0, 16, s) != hipSuccess ||
-        hipMemcpyAsync(mm, mm_empty, 64, hipMemcpyHostToDevice, s) != hipSuccess) {
-      rc = fail("memset");
-      break;
-    }
+    if (hipMemsetAsync(B.ovf, 0, 16, s) != hipSuccess ||
+        hipMemcpyAsync(B.mm, mm_empty, 64, hipMemcpyHostToDevice, s) != hipSuccess)
+      return fail("memset");
     prewalk(true);
-    if (hipMemsetAsync(k.terr, 0, n * 4, s) != hipSuccess) {
-      rc = fail("memset");
-      break;
-    }
-    // 2b. renumber position-major: ipos = the sorted keys, the rest gathered
-    // (keys read from the records, values counted: no key / index arrays)
-    {
-      size_t tb0 = tmp_bytes;
-      if (rocprim::radix_sort_pairs(tmp, tb0, rocprim::make_transform_iterator((const uint4 *)k.erec, PosOf()),
-                                    k.ipos, rocprim::make_counting_iterator<uint32_t>(0u), qids, (size_t)M, 0,
-                                    bits_for(std::max<size_t>(1, pl.pos.size()) - 1), s) != hipSuccess) {
-        rc = fail("position sort");
-        break;
-      }
-    }
-    hipLaunchKernelGGL(k_perm_inv, dim3(grid_for(M)), dim3(kT), 0, s, k, qids, inv);
-    hipLaunchKernelGGL(k_own, dim3(grid_for(M)), dim3(kT), 0, s, k, (const uint32_t *)inv);
+    if (hipMemsetAsync(k.terr, 0, n * 4, s) != hipSuccess) return fail("memset");
+    return 0;
+  }
+
+  // 2c. renumber position-major: ipos = the sorted keys, the rest gathered
+  // (keys read from the records, values counted: no key / index arrays);
+  // own errors, entry items, replicas
+  int renumber() {
+    size_t tb = tmp_bytes;
+    if (rocprim::radix_sort_pairs(B.tmp, tb, rocprim::make_transform_iterator((const uint4 *)k.erec, PosOf()), k.ipos,
+                                  rocprim::make_counting_iterator<uint32_t>(0u), B.qids, (size_t)M, 0,
+                                  bits_for(std::max<size_t>(1, pl.pos.size()) - 1), s) != hipSuccess)
+      return fail("position sort");
+    hipLaunchKernelGGL(k_perm_inv, dim3(grid_for(M)), dim3(kT), 0, s, k, B.qids, B.inv);
+    hipLaunchKernelGGL(k_own, dim3(grid_for(M)), dim3(kT), 0, s, k, (const uint32_t *)B.inv);
     hipLaunchKernelGGL(k_root500, dim3(grid_for(n)), dim3(kT), 0, s, k);
-    hipLaunchKernelGGL(k_perm_apply, dim3(grid_for(M)), dim3(kT), 0, s, k, qids);
+    hipLaunchKernelGGL(k_perm_apply, dim3(grid_for(M)), dim3(kT), 0, s, k, B.qids);
     if (pl.modeb) {
-      if (hipMemsetAsync(ifst, 0xFF, M * 4, s) != hipSuccess) {
-        rc = fail("memset");
-        break;
-      }
+      if (hipMemsetAsync(B.ifst, 0xFF, M * 4, s) != hipSuccess) return fail("memset");
       hipLaunchKernelGGL(k_fail, dim3(grid_for(M)), dim3(kT), 0, s, k);
     }
-    hipLaunchKernelGGL(k_roots, dim3(grid_for(n)), dim3(kT), 0, s, k, inv);
+    hipLaunchKernelGGL(k_roots, dim3(grid_for(n)), dim3(kT), 0, s, k, B.inv);
     hipLaunchKernelGGL(k_reps, dim3(grid_for(M)), dim3(kT), 0, s, k);
     if (pl.cyclic) {  // the first pass's cut step begins: contention-free callee maxima (k_relmax)
-      if (hipMemsetAsync(k.acc, 0, M * 8 * k.aw, s) != hipSuccess) {
-        rc = fail("memset");
-        break;
-      }
-      hipLaunchKernelGGL(k_relmax, dim3(grid_for(M)), dim3(kT), 0, s, k, qids, (unsigned long long *)k.acc);
+      if (hipMemsetAsync(k.acc, 0, M * 8 * k.aw, s) != hipSuccess) return fail("memset");
+      hipLaunchKernelGGL(k_relmax, dim3(grid_for(M)), dim3(kT), 0, s, k, B.qids, (unsigned long long *)k.acc);
     }
-    // 3. buckets
-    if (hipMemcpyAsync(d_row_hold, row_hold.data(), rows_n * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
-      rc = fail("hold table upload");
-      break;
-    }
-    k.row_hold = d_row_hold;
+    return 0;
+  }
+
+  // 3. buckets: the rounds' and finish groups' item lists, the step-begin ops by round
+  int buckets() {
+    if (hipMemcpyAsync(B.d_row_hold, row_hold.data(), row_hold.size() * 8, hipMemcpyHostToDevice, s) != hipSuccess)
+      return fail("hold table upload");
+    k.row_hold = B.d_row_hold;
     // the step-begin ops; each position's item range (k.ipos is sorted)
-    hipLaunchKernelGGL(k_bucket_keys, dim3(grid_for(M)), dim3(kT), 0, s, k, op_k, op_v, ovf + 3);
+    hipLaunchKernelGGL(k_bucket_keys, dim3(grid_for(M)), dim3(kT), 0, s, k, B.op_k, B.op_v, B.ovf + 3);
     const uint32_t NP = (uint32_t)pl.pos.size();
-    hipLaunchKernelGGL(k_bounds, dim3(grid_for(M + 1)), dim3(kT), 0, s, (const uint32_t *)k.ipos, M, NP, 0u, d_poff);
+    hipLaunchKernelGGL(k_bounds, dim3(grid_for(M + 1)), dim3(kT), 0, s, (const uint32_t *)k.ipos, M, NP, 0u, B.d_poff);
     uint32_t n_ops = 0;
     std::vector<uint32_t> poff(NP + 1);
-    if (hipMemcpyAsync(&n_ops, ovf + 3, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(poff.data(), d_poff, (NP + 1) * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        sync_s() != hipSuccess) {
-      rc = fail("bucket read-back");
-      break;
-    }
+    if (hipMemcpyAsync(&n_ops, B.ovf + 3, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(poff.data(), B.d_poff, (NP + 1) * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        sync_s() != hipSuccess)
+      return fail("bucket read-back");
     // the rounds' and groups' lists: positions in increasing order within each
     std::vector<uint32_t> qdst(NP), fdst(NP);
-    {
-      std::vector<uint64_t> qn(R + 1, 0), fn(G + 1, 0);
-      for (uint32_t v = 0; v < NP; ++v) {
-        qn[pl.item_pos[v].qround + 1] += poff[v + 1] - poff[v];
-        fn[pl.item_pos[v].fgroup + 1] += poff[v + 1] - poff[v];
-      }
-      for (uint32_t r = 0; r < R; ++r) qn[r + 1] += qn[r];
-      for (uint32_t g = 0; g < G; ++g) fn[g + 1] += fn[g];
-      for (uint32_t r = 0; r <= R; ++r) qoff[r] = (uint32_t)qn[r];
-      for (uint32_t g = 0; g <= G; ++g) foff[g] = (uint32_t)fn[g];
-      for (uint32_t v = 0; v < NP; ++v) {
-        const uint32_t c = poff[v + 1] - poff[v];
-        qdst[v] = (uint32_t)qn[pl.item_pos[v].qround];
-        qn[pl.item_pos[v].qround] += c;
-        fdst[v] = (uint32_t)fn[pl.item_pos[v].fgroup];
-        fn[pl.item_pos[v].fgroup] += c;
-      }
+    std::vector<uint64_t> qc(R + 1, 0), fc(G + 1, 0);
+    for (uint32_t v = 0; v < NP; ++v) {
+      qc[pl.item_pos[v].qround + 1] += poff[v + 1] - poff[v];
+      fc[pl.item_pos[v].fgroup + 1] += poff[v + 1] - poff[v];
     }
-    if (hipMemcpyAsync(d_qdst, qdst.data(), NP * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_fdst, fdst.data(), NP * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
-      rc = fail("list upload");
-      break;
+    for (uint32_t r = 0; r < R; ++r) qc[r + 1] += qc[r];
+    for (uint32_t g = 0; g < G; ++g) fc[g + 1] += fc[g];
+    qoff.assign(qc.begin(), qc.end());
+    foff.assign(fc.begin(), fc.end());
+    for (uint32_t v = 0; v < NP; ++v) {
+      const uint32_t c = poff[v + 1] - poff[v];
+      qdst[v] = (uint32_t)qc[pl.item_pos[v].qround];
+      qc[pl.item_pos[v].qround] += c;
+      fdst[v] = (uint32_t)fc[pl.item_pos[v].fgroup];
+      fc[pl.item_pos[v].fgroup] += c;
     }
-    hipLaunchKernelGGL(k_scatter_ids, dim3(grid_for(M)), dim3(kT), 0, s, k, d_poff, d_qdst, d_fdst, qids, fids);
-    size_t tb = tmp_bytes;
-    std::vector<uint32_t> soff(R + 1, 0);
+    if (hipMemcpyAsync(B.d_qdst, qdst.data(), NP * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(B.d_fdst, fdst.data(), NP * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+      return fail("list upload");
+    hipLaunchKernelGGL(k_scatter_ids, dim3(grid_for(M)), dim3(kT), 0, s, k, B.d_poff, B.d_qdst, B.d_fdst, B.qids,
+                       B.fids);
+    soff.assign(R + 1, 0);
     if (n_ops) {
-      if (rocprim::radix_sort_pairs(tmp, tb, op_k, op_k2, op_v, op_v2, (size_t)n_ops, 0, bits_for(R), s) != hipSuccess) {
-        rc = fail("step-op sort");
-        break;
-      }
-      hipLaunchKernelGGL(k_bounds, dim3(grid_for(n_ops + 1)), dim3(kT), 0, s, op_k2, (uint64_t)n_ops, R, 0u, d_soff);
-      if (hipMemcpyAsync(soff.data(), d_soff, (R + 1) * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-          sync_s() != hipSuccess) {
-        rc = fail("step-op offsets read-back");
-        break;
-      }
+      size_t tb = tmp_bytes;
+      if (rocprim::radix_sort_pairs(B.tmp, tb, B.op_k, B.op_k2, B.op_v, B.op_v2, (size_t)n_ops, 0, bits_for(R), s) !=
+          hipSuccess)
+        return fail("step-op sort");
+      hipLaunchKernelGGL(k_bounds, dim3(grid_for(n_ops + 1)), dim3(kT), 0, s, B.op_k2, (uint64_t)n_ops, R, 0u,
+                         B.d_soff);
+      if (hipMemcpyAsync(soff.data(), B.d_soff, (R + 1) * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+          sync_s() != hipSuccess)
+        return fail("step-op offsets read-back");
     }
-    const uint32_t row_bits = bits_for(max_row);
-    // ISIM_FLAG_DES_TWO_SORTS: always the two-sort queue path (an independent check)
-    const bool two_sorts = (L.flags & ISIM_FLAG_DES_TWO_SORTS) != 0;
-    constexpr uint32_t stats_span = kQSpan;
-    // 4. rounds; a cyclic schedule: quiet passes from zero (a lower bound of
-    // every time: the iteration only raises values) until no stored value
-    // changes, then the pass that records the statistics (des.hip des_launch)
-    // callee maxima: restarted from zero for every item a pass recomputes (a
-    // start can move down when the order of a queue changes, so maxima are
-    // never carried over); a cut step begin reads the last computed ones
-    // (k_acc_init moves them to acc_prev).  After the first pass a quiet pass
-    // recomputes only the items of the trace chunks the previous pass
-    // changed (k.dcur)
-    uint32_t qn = 0;       // k_qarr launches: the arrival-range slot alternates
-    // ISIM_FLAG_DES_SORT_ALL: never reuse a kept order (an independent check)
-    const bool keep_ord = pl.cyclic && !(L.flags & ISIM_FLAG_DES_SORT_ALL);
-    std::vector<uint8_t> have_ord(R, 0);
-    std::vector<uint64_t> rlo(R, ~0ull), rhi(R, 0);  // per sort round: its arrival range over the passes
-    // k_qscan's states (their epochs: 1, 2, ... per launch) and ticket
-    if (qscan && (hipMemsetAsync(qstate, 0, al256((M + 511) / 512 * sizeof(QState)), s) != hipSuccess ||
-                  hipMemsetAsync(qticket, 0, 4, s) != hipSuccess)) {
-      rc = fail("memset");
-      break;
+    return 0;
+  }
+
+  // 4b. the queues of round r (its m > 0 items): arrivals, the FIFO order
+  // (kept, in list order, one sort or two), one segmented max-plus scan.
+  // Returns early, with the starts as they are, when a quiet pass finds every
+  // arrival of the round unchanged.
+  int round_queue(K &kk, uint32_t r, uint64_t m, uint32_t span) {
+    uint32_t *const list = B.qids + qoff[r], *const ord = B.ord + qoff[r];
+    uint16_t *const ordc = B.ordc + qoff[r];
+    const bool nosort = pl.round_nosort[r] && !two_sorts;
+    // (a no-sort round reads no arrival range back; k_qscan computes its arrivals)
+    uint64_t *slot = B.mm + 4 * (qn & 1u), *slot_next = B.mm + 4 * ((qn + 1) & 1u);
+    const bool chk = !nosort && have_ord[r];
+    if (!(nosort && qscan)) {
+      ++qn;
+      hipLaunchKernelGGL(k_qarr, dim3(grid_for(m)), dim3(kT), 0, s, kk, list, m, (unsigned long long *)slot,
+                         (unsigned long long *)slot_next);
+      if (chk)  // (its flag in the same slot: one read-back)
+        hipLaunchKernelGGL(k_ordchk, dim3(grid_for(m)), dim3(kT), 0, s, kk, (const uint32_t *)list,
+                           (const uint32_t *)ord, (const uint16_t *)ordc, m, (unsigned long long *)slot);
     }
-    auto pass = [&](K &kk) {
-    hipLaunchKernelGGL(k_acc_init, dim3(grid_for(M)), dim3(kT), 0, s, kk, pl.cyclic ? acc_b : nullptr, kk.acc);
+    // a quiet pass after the first: a round whose arrivals all equal the
+    // previous pass's keeps its starts (its queues are skipped)
+    // (sort rounds only: they read the range back anyway; a sort-free
+    // round would pay a stream synchronisation for the check)
+    const bool may_skip = kk.quiet && !kk.first && !nosort;
+    // range, change flag, kept-order flag (k_ordchk)
+    uint64_t hmm[4] = {0, 0, 1, 1};
+    if ((!nosort || may_skip) &&
+        (hipMemcpyAsync(hmm, slot, 32, hipMemcpyDeviceToHost, s) != hipSuccess || sync_s() != hipSuccess))
+      return fail("arrival range read-back");
+    const bool bad = hmm[3] != 0;
+    if (may_skip && !hmm[2]) return 0;
+    if (!nosort) {
+      // the round's arrival range over the passes: the items a pass does
+      // not recompute keep their arrivals (a superset range is a valid key)
+      rlo[r] = std::min<uint64_t>(rlo[r], hmm[0]);
+      rhi[r] = std::max<uint64_t>(rhi[r], hmm[1]);
+      hmm[0] = rlo[r];
+      hmm[1] = rhi[r];
+    }
+    const uint32_t ab = bits_for(hmm[1] - hmm[0]);
+    size_t tb = tmp_bytes;
+    // k_qscan's source of the round's order (k_pairs* only for the two-sort path)
+    QSrc qsrc{list, ord, B.key_b, B.val_b, hmm[0], rep_bits, ab, B.rk_a, B.rk_b, B.sid, B.mp_in};
+    int qsk = kQArrays;
+    if (chk && !bad) {  // the kept order holds: no sort
+      qsk = kQKept;
+      if (!qscan)
+        hipLaunchKernelGGL(k_pairs1o, dim3(grid_for(m)), dim3(kT), 0, s, kk, m, (const uint32_t *)ord,
+                           (const uint32_t *)list, rep_bits, B.rk_a, B.rk_b, B.mp_in, B.sid);
+    } else if (nosort) {
+      qsk = kQList;
+      if (!qscan)  // k_qscan reads the list itself
+        hipLaunchKernelGGL(k_pairs0, dim3(grid_for(m)), dim3(kT), 0, s, kk, list, m, B.rk_a, B.rk_b, B.mp_in, B.sid);
+    } else if (!two_sorts && row_bits + rep_bits + ab <= 64) {
+      hipLaunchKernelGGL(k_qkey1, dim3(grid_for(m)), dim3(kT), 0, s, kk, list, m, hmm[0], rep_bits, ab, B.key_a,
+                         B.val_a);
+      if (rocprim::radix_sort_pairs(B.tmp, tb, B.key_a, B.key_b, B.val_a, B.val_b, (size_t)m, 0,
+                                    row_bits + rep_bits + ab, s) != hipSuccess)
+        return fail("queue sort");
+      hipLaunchKernelGGL(k_tiefix<true>, dim3(grid_for(m)), dim3(kT), 0, s, kk, (const uint64_t *)B.key_b, B.val_b, m,
+                         (const uint32_t *)list);
+      if (keep_ord) {  // the next pass checks this order first
+        hipLaunchKernelGGL(k_keep_ord, dim3(grid_for(m)), dim3(kT), 0, s, kk, (const uint32_t *)B.val_b,
+                           (const uint32_t *)list, m, ord, ordc);
+        have_ord[r] = 1;
+      }
+      qsk = kQSorted;
+      if (!qscan)
+        hipLaunchKernelGGL(k_pairs1, dim3(grid_for(m)), dim3(kT), 0, s, kk, m, B.key_b, B.val_b,
+                           (const uint32_t *)list, rep_bits, ab, hmm[0], B.rk_a, B.rk_b, B.mp_in, B.sid);
+    } else {
+      hipLaunchKernelGGL(k_qkey2, dim3(grid_for(m)), dim3(kT), 0, s, kk, list, m, hmm[0], rep_bits, B.key_a, B.val_a,
+                         B.ovf);
+      if (rocprim::radix_sort_pairs(B.tmp, tb, B.key_a, B.key_b, B.val_a, B.val_b, (size_t)m, 0, 64, s) != hipSuccess)
+        return fail("arrival sort");
+      // ties of (replica, arrival) by (trace, hop); the stable row sort keeps them
+      hipLaunchKernelGGL(k_tiefix<false>, dim3(grid_for(m)), dim3(kT), 0, s, kk, (const uint64_t *)B.key_b, B.val_b, m,
+                         (const uint32_t *)nullptr);
+      hipLaunchKernelGGL(k_rkeys, dim3(grid_for(m)), dim3(kT), 0, s, kk, B.val_b, m, B.rk_a, B.rv_a);
+      tb = tmp_bytes;
+      if (rocprim::radix_sort_pairs(B.tmp, tb, B.rk_a, B.rk_b, B.rv_a, B.rv_b, (size_t)m, 0, row_bits, s) != hipSuccess)
+        return fail("service sort");
+      hipLaunchKernelGGL(k_pairs2, dim3(grid_for(m)), dim3(kT), 0, s, kk, m, B.rk_b, B.rv_b, B.key_b, B.val_b, rep_bits,
+                         B.rk_a, B.mp_in, B.sid);
+    }
+    if (qscan) {
+      // 8 items per lane on a large round, 2 otherwise (more tiles to spread)
+      const bool big = m >= 2048ull * 512;
+      const uint32_t tiles = (uint32_t)((m + (big ? 2047 : 511)) / (big ? 2048 : 512));
+      if (qtbase > 0xFFFFFFFFu - tiles) {  // the ticket counter restarts
+        if (hipMemsetAsync(B.qticket, 0, 4, s) != hipSuccess) return fail("memset");
+        qtbase = 0;
+      }
+      ++qepoch;
+      static void (*const qs_k[2][4])(K, uint64_t, QSrc, QState *, uint32_t *, uint32_t, uint32_t) = {
+          {k_qscan<2, kQArrays>, k_qscan<2, kQList>, k_qscan<2, kQKept>, k_qscan<2, kQSorted>},
+          {k_qscan<8, kQArrays>, k_qscan<8, kQList>, k_qscan<8, kQKept>, k_qscan<8, kQSorted>}};
+      hipLaunchKernelGGL(qs_k[big][qsk], dim3(tiles), dim3(kT), 0, s, kk, m, qsrc, B.qstate, B.qticket, qtbase, qepoch);
+      qtbase += tiles;
+    } else {
+      tb = tmp_bytes;
+      if (rocprim::inclusive_scan_by_key(B.tmp, tb, B.rk_a, B.mp_in, B.mp_out, (size_t)m, MPThen(),
+                                         rocprim::equal_to<uint32_t>(), s) != hipSuccess)
+        return fail("queue scan");
+      hipLaunchKernelGGL(k_qout, dim3(grid_for((m + span - 1) / span)), dim3(kT), 0, s, kk, m, B.rk_b, B.sid, B.mp_in,
+                         B.mp_out, span);
+    }
+    return 0;
+  }
+
+  // 4. one pass over the rounds: step begins (4a), queues (4b), finishes (4c).
+  // Callee maxima restart from zero for every item a pass recomputes (a
+  // start can move down when the order of a queue changes, so maxima are
+  // never carried over); a cut step begin reads the last computed ones
+  // (k_acc_init moves them to acc_prev)
+  int pass(K &kk) {
+    hipLaunchKernelGGL(k_acc_init, dim3(grid_for(M)), dim3(kT), 0, s, kk, pl.cyclic ? B.acc_b : nullptr, kk.acc);
     // items per lane of k_qout / k_fin: runs of one row / position summed
     // before the statistics atomics; a quiet pass records none, and one item
     // per lane gives its finish groups (~0.8 M items on c4d) 16x the waves
-    const uint32_t span = kk.quiet ? 1u : stats_span;
-    for (uint32_t r = 0; r < R && !rc; ++r) {
+    const uint32_t span = kk.quiet ? 1u : kQSpan;
+    for (uint32_t r = 0; r < R; ++r) {
       if (soff[r + 1] > soff[r])
-        hipLaunchKernelGGL(k_steps, dim3(grid_for(soff[r + 1] - soff[r])), dim3(kT), 0, s, kk, op_v2 + soff[r],
+        hipLaunchKernelGGL(k_steps, dim3(grid_for(soff[r + 1] - soff[r])), dim3(kT), 0, s, kk, B.op_v2 + soff[r],
                            (uint64_t)(soff[r + 1] - soff[r]));
-      const uint64_t m = qoff[r + 1] - qoff[r];
-      if (m) {
-        const bool nosort = pl.round_nosort[r] && !two_sorts;
-        // (a no-sort round reads no arrival range back; k_qscan computes its arrivals)
-        uint64_t *slot = mm + 4 * (qn & 1u), *slot_next = mm + 4 * ((qn + 1) & 1u);
-        const bool chk = !nosort && have_ord[r];
-        if (!(nosort && qscan)) {
-          ++qn;
-          hipLaunchKernelGGL(k_qarr, dim3(grid_for(m)), dim3(kT), 0, s, kk, qids + qoff[r], m,
-                             (unsigned long long *)slot, (unsigned long long *)slot_next);
-          if (chk)  // (its flag in the same slot: one read-back)
-            hipLaunchKernelGGL(k_ordchk, dim3(grid_for(m)), dim3(kT), 0, s, kk, (const uint32_t *)(qids + qoff[r]),
-                               (const uint32_t *)(ord + qoff[r]), (const uint16_t *)(ordc + qoff[r]), m,
-                               (unsigned long long *)slot);
-        }
-        // a quiet pass after the first: a round whose arrivals all equal the
-        // previous pass's keeps its starts (its queues are skipped)
-        // (sort rounds only: they read the range back anyway; a sort-free
-        // round would pay a stream synchronisation for the check)
-        const bool may_skip = kk.quiet && !kk.first && !nosort;
-        // range, change flag, kept-order flag (k_ordchk)
-        uint64_t hmm[4] = {0, 0, 1, 1};
-        if ((!nosort || may_skip) &&
-            (hipMemcpyAsync(hmm, slot, 32, hipMemcpyDeviceToHost, s) != hipSuccess || sync_s() != hipSuccess)) {
-          rc = fail("arrival range read-back");
-          break;
-        }
-        const bool bad = hmm[3] != 0;
-        if (may_skip && !hmm[2]) {
-          goto finishes;
-        }
-        if (!nosort) {
-          // the round's arrival range over the passes: the items a pass does
-          // not recompute keep their arrivals (a superset range is a valid key)
-          rlo[r] = std::min<uint64_t>(rlo[r], hmm[0]);
-          rhi[r] = std::max<uint64_t>(rhi[r], hmm[1]);
-          hmm[0] = rlo[r];
-          hmm[1] = rhi[r];
-        }
-        const uint32_t ab = bits_for(hmm[1] - hmm[0]);
-        tb = tmp_bytes;
-        // k_qscan's source of the round's order (k_pairs* only for the two-sort path)
-        QSrc qsrc{qids + qoff[r], ord + qoff[r], key_b, val_b, hmm[0], rep_bits, ab, rk_a, rk_b, sid, mp_in};
-        int qsk = kQArrays;
-        if (chk && !bad) {  // the kept order holds: no sort
-          qsk = kQKept;
-          if (!qscan)
-            hipLaunchKernelGGL(k_pairs1o, dim3(grid_for(m)), dim3(kT), 0, s, kk, m, (const uint32_t *)(ord + qoff[r]),
-                               (const uint32_t *)(qids + qoff[r]), rep_bits, rk_a, rk_b, mp_in, sid);
-        } else if (nosort) {
-          qsk = kQList;
-          if (!qscan)  // k_qscan reads the list itself
-            hipLaunchKernelGGL(k_pairs0, dim3(grid_for(m)), dim3(kT), 0, s, kk, qids + qoff[r], m, rk_a, rk_b,
-                               mp_in, sid);
-        } else if (!two_sorts && row_bits + rep_bits + ab <= 64) {
-          hipLaunchKernelGGL(k_qkey1, dim3(grid_for(m)), dim3(kT), 0, s, kk, qids + qoff[r], m, hmm[0], rep_bits, ab,
-                             key_a, val_a);
-          if (rocprim::radix_sort_pairs(tmp, tb, key_a, key_b, val_a, val_b, (size_t)m, 0, row_bits + rep_bits + ab,
-                                        s) != hipSuccess) {
-            rc = fail("queue sort");
-            break;
-          }
-          hipLaunchKernelGGL(k_tiefix<true>, dim3(grid_for(m)), dim3(kT), 0, s, kk, (const uint64_t *)key_b, val_b, m,
-                             (const uint32_t *)(qids + qoff[r]));
-          if (keep_ord) {  // the next pass checks this order first
-            hipLaunchKernelGGL(k_keep_ord, dim3(grid_for(m)), dim3(kT), 0, s, kk, (const uint32_t *)val_b,
-                               (const uint32_t *)(qids + qoff[r]), m, ord + qoff[r], ordc + qoff[r]);
-            have_ord[r] = 1;
-          }
-          qsk = kQSorted;
-          if (!qscan)
-            hipLaunchKernelGGL(k_pairs1, dim3(grid_for(m)), dim3(kT), 0, s, kk, m, key_b, val_b,
-                               (const uint32_t *)(qids + qoff[r]), rep_bits, ab, hmm[0], rk_a, rk_b, mp_in, sid);
-        } else {
-          hipLaunchKernelGGL(k_qkey2, dim3(grid_for(m)), dim3(kT), 0, s, kk, qids + qoff[r], m, hmm[0], rep_bits,
-                             key_a, val_a, ovf);
-          if (rocprim::radix_sort_pairs(tmp, tb, key_a, key_b, val_a, val_b, (size_t)m, 0, 64, s) != hipSuccess) {
-            rc = fail("arrival sort");
-            break;
-          }
-          // ties of (replica, arrival) by (trace, hop); the stable row sort keeps them
-          hipLaunchKernelGGL(k_tiefix<false>, dim3(grid_for(m)), dim3(kT), 0, s, kk, (const uint64_t *)key_b, val_b, m,
-                             (const uint32_t *)nullptr);
-          hipLaunchKernelGGL(k_rkeys, dim3(grid_for(m)), dim3(kT), 0, s, kk, val_b, m, rk_a, rv_a);
-          tb = tmp_bytes;
-          if (rocprim::radix_sort_pairs(tmp, tb, rk_a, rk_b, rv_a, rv_b, (size_t)m, 0, row_bits, s) != hipSuccess) {
-            rc = fail("service sort");
-            break;
-          }
-          hipLaunchKernelGGL(k_pairs2, dim3(grid_for(m)), dim3(kT), 0, s, kk, m, rk_b, rv_b, key_b, val_b, rep_bits,
-                             rk_a, mp_in, sid);
-        }
-        if (qscan) {
-          // 8 items per lane on a large round, 2 otherwise (more tiles to spread)
-          const bool big = m >= 2048ull * 512;
-          const uint32_t tiles = (uint32_t)((m + (big ? 2047 : 511)) / (big ? 2048 : 512));
-          if (qtbase > 0xFFFFFFFFu - tiles) {  // the ticket counter restarts
-            if (hipMemsetAsync(qticket, 0, 4, s) != hipSuccess) {
-              rc = fail("memset");
-              break;
-            }
-            qtbase = 0;
-          }
-          ++qepoch;
-          static void (*const qs_k[2][4])(K, uint64_t, QSrc, QState *, uint32_t *, uint32_t, uint32_t) = {
-              {k_qscan<2, kQArrays>, k_qscan<2, kQList>, k_qscan<2, kQKept>, k_qscan<2, kQSorted>},
-              {k_qscan<8, kQArrays>, k_qscan<8, kQList>, k_qscan<8, kQKept>, k_qscan<8, kQSorted>}};
-          hipLaunchKernelGGL(qs_k[big][qsk], dim3(tiles), dim3(kT), 0, s, kk, m, qsrc, qstate, qticket, qtbase,
-                             qepoch);
-          qtbase += tiles;
-        } else {
-          tb = tmp_bytes;
-          if (rocprim::inclusive_scan_by_key(tmp, tb, rk_a, mp_in, mp_out, (size_t)m, MPThen(),
-                                             rocprim::equal_to<uint32_t>(), s) != hipSuccess) {
-            rc = fail("queue scan");
-            break;
-          }
-          hipLaunchKernelGGL(k_qout, dim3(grid_for((m + span - 1) / span)), dim3(kT), 0, s, kk, m, rk_b, sid,
-                             mp_in, mp_out, span);
-        }
+      if (const uint64_t m = qoff[r + 1] - qoff[r]) {
+        if (int rc = round_queue(kk, r, m, span)) return rc;
       }
-    finishes:
       for (uint32_t gi = pl.fin_round_off[r]; gi < pl.fin_round_off[r + 1]; ++gi) {
         const uint64_t mg = foff[gi + 1] - foff[gi];
         if (mg) hipLaunchKernelGGL(k_fin, dim3(grid_for((mg + span - 1) / span)), dim3(kT), 0, s, kk,
-                                   fids + foff[gi], mg, span);  // grid_for(ceil(mg / span)) blocks of kT: >= the chunks
+                                   B.fids + foff[gi], mg, span);  // grid_for(ceil(mg / span)) blocks of kT: >= the chunks
       }
     }
-    };
+    return 0;
+  }
+
+  // A cyclic schedule: quiet passes from zero (a lower bound of every time:
+  // the iteration only raises values) until no stored value changes, then the
+  // pass that records the statistics (des.hip des_launch).  After the first
+  // pass a quiet pass recomputes only the items of the traces the previous
+  // pass changed (k.dcur, k.dcur_t)
+  int fixed_point() {
+    // k_qscan's states and ticket
+    if (qscan && (hipMemsetAsync(B.qstate, 0, (M + kQTile - 1) / kQTile * sizeof(QState), s) != hipSuccess ||
+                  hipMemsetAsync(B.qticket, 0, 4, s) != hipSuccess))
+      return fail("memset");
     if (pl.cyclic) {
       if (hipMemsetAsync(k.IS, 0, M * 8, s) != hipSuccess || hipMemsetAsync(k.IF, 0, M * 8, s) != hipSuccess ||
-          (k.bw && hipMemsetAsync(k.bk, 0, M * 8 * k.bw, s) != hipSuccess)) {
-        rc = fail("memset");
-        break;
-      }
+          (k.bw && hipMemsetAsync(k.bk, 0, M * 8 * k.bw, s) != hipSuccess))
+        return fail("memset");
       K kq = k;
       kq.quiet = 1;
-      kq.acc_prev = acc_b;
-      kq.changed = chg;
+      kq.acc_prev = B.acc_b;
+      kq.changed = B.chg;
       uint32_t p = 0;
-      for (; p < kMaxPasses && !rc; ++p) {
+      for (; p < kMaxPasses; ++p) {
         uint32_t changed[2] = {1, 0};
-        if (hipMemsetAsync(kq.changed, 0, 8, s) != hipSuccess || hipMemsetAsync(chg_b, 0, n_chunks, s) != hipSuccess ||
-            hipMemsetAsync(chg_tb, 0, n, s) != hipSuccess) {
-          rc = fail("memset");
-          break;
-        }
+        if (hipMemsetAsync(kq.changed, 0, 8, s) != hipSuccess ||
+            hipMemsetAsync(B.chg_b, 0, dims.n_chunks(), s) != hipSuccess ||
+            hipMemsetAsync(B.chg_tb, 0, n, s) != hipSuccess)
+          return fail("memset");
         kq.first = p == 0 ? 1u : 0u;
         // the first pass recomputes everything; later ones the chunks the
         // previous pass changed
-        kq.dcur = p == 0 ? nullptr : chg_a;
-        kq.dnext = chg_b;
-        kq.dcur_t = chg_ta;
-        kq.dnext_t = chg_tb;
-        pass(kq);
-        if (rc) break;
-        std::swap(chg_a, chg_b);
-        std::swap(chg_ta, chg_tb);
-        if (hipMemcpyAsync(changed, kq.changed, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            sync_s() != hipSuccess) {
-          rc = fail("fixed-point read-back");
-          break;
-        }
+        kq.dcur = p == 0 ? nullptr : B.chg_a;
+        kq.dnext = B.chg_b;
+        kq.dcur_t = B.chg_ta;
+        kq.dnext_t = B.chg_tb;
+        if (int rc = pass(kq)) return rc;
+        std::swap(B.chg_a, B.chg_b);
+        std::swap(B.chg_ta, B.chg_tb);
+        if (hipMemcpyAsync(changed, kq.changed, 8, hipMemcpyDeviceToHost, s) != hipSuccess || sync_s() != hipSuccess)
+          return fail("fixed-point read-back");
         rep.passes = p + 2;  // the quiet passes so far and the recording pass
         if (!changed[0]) break;
       }
-      if (!rc && p == kMaxPasses) {
+      if (p == kMaxPasses) {
         static const uint32_t one = 1;
-        if (hipMemcpyAsync(ovf + 1, &one, 4, hipMemcpyHostToDevice, s) != hipSuccess) rc = fail("flag");
+        if (hipMemcpyAsync(B.ovf + 1, &one, 4, hipMemcpyHostToDevice, s) != hipSuccess) return fail("flag");
       }
-      if (rc) break;
     }
-    k.acc_prev = acc_b;
-    pass(k);  // dcur null: every item
-    if (rc) break;
-    // 5. records and statistics
+    k.acc_prev = B.acc_b;
+    return pass(k);  // dcur null: every item
+  }
+
+  // 5. records and statistics
+  int finalize() {
     hipLaunchKernelGGL(k_final, dim3(grid_for(n, 1024)), dim3(kT), 0, s, k);
-    hipLaunchKernelGGL(k_flag_retry, dim3(1), dim3(1), 0, s, k.stats, ovf);
-    if (hipGetLastError() != hipSuccess) {
-      rc = fail("kernel launch");
-      break;
-    }
+    hipLaunchKernelGGL(k_flag_retry, dim3(1), dim3(1), 0, s, k.stats, B.ovf);
+    if (hipGetLastError() != hipSuccess) return fail("kernel launch");
     // a look-back that gave up (k_qscan) fails the batch loudly: nothing was
     // accumulated (k_final) and the call returns the error
     uint32_t fault = 0;
-    if (hipMemcpyAsync(&fault, ovf + 2, 4, hipMemcpyDeviceToHost, s) != hipSuccess || sync_s() != hipSuccess) {
-      rc = fail("fault read-back");
-      break;
-    }
+    if (hipMemcpyAsync(&fault, B.ovf + 2, 4, hipMemcpyDeviceToHost, s) != hipSuccess || sync_s() != hipSuccess)
+      return fail("fault read-back");
     if (fault)
-      rc = fail("a queue scan's look-back gave up waiting for an earlier tile (k_qscan): the batch was not "
-                "accumulated");
-  } while (0);
-  return rc;
+      return fail("a queue scan's look-back gave up waiting for an earlier tile (k_qscan): the batch was not "
+                  "accumulated");
+    return 0;
+  }
+};
+
+}  // namespace
+
+uint64_t des_items_workspace_bytes(uint64_t n) {
+  Arena sizing;
+  ItemTraceBufs t;
+  des_items_trace_layout(sizing, t, n, scan_u64_bytes(n));
+  return sizing.bytes();
+}
+
+int des_items_launch(const DesItemsLaunch &L, void *stream, std::string &err) {
+  return Batch(L, (hipStream_t)stream, err).run();
 }
 
 }  // namespace isim

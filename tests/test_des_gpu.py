@@ -162,6 +162,36 @@ def test_device_entry_accumulates(gpu, wide):
     assert np.array_equal(tg, want)
 
 
+@pytest.mark.parametrize("case", ["static_narrow", "static_wide", "items"])
+def test_device_entry_stays_inside_workspace(gpu, case):
+    """A workspace of exactly workspace_bytes(n) with a 4 KiB canary behind it:
+    both engines leave the canary untouched and accumulate what serve() does
+    (the layouts of des_layout.h are what isim_des_workspace_bytes sizes)."""
+    import torch
+    from test_des_items_gpu import _zero_hold_mix
+    if case == "items":
+        c = DesCase(_zero_hold_mix(), 3_000_000)
+        assert c.d.info.items == 1
+    else:
+        c = DesCase(_sleepy_tree(3, 4, reps_leaves=3), 3_000_000)
+        assert c.d.info.items == 0
+    n, guard = 3000, 4096
+    dev = torch.device("cuda", 0)
+    st = torch.zeros(c.h.stats_words, dtype=torch.int64, device=dev)
+    tab = torch.zeros(max(1, c.d.table_words), dtype=torch.int64, device=dev)
+    wsb = c.d.workspace_bytes(n)
+    assert wsb % 256 == 0
+    ws = torch.empty(wsb + guard, dtype=torch.uint8, device=dev)
+    ws[wsb:] = 0xA5
+    c.d.serve_device(0, n, 0, st.data_ptr(), tab.data_ptr(), ws.data_ptr(), wsb,
+                     torch.cuda.current_stream().cuda_stream, wide=case == "static_wide")
+    torch.cuda.synchronize()
+    assert bool((ws[wsb:] == 0xA5).all()), "the engine wrote past workspace_bytes(n)"
+    _, s0, t0 = c.d.serve(0, n, records=False)
+    assert np.array_equal(st.cpu().numpy().view(np.uint64), s0)
+    assert np.array_equal(tab.cpu().numpy().view(np.uint64)[:t0.size], t0)
+
+
 # ---- the sort path: DAG graphs (a service at several positions per trace)
 # and replicated callers (arrivals out of trace order)
 
