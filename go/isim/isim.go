@@ -194,6 +194,62 @@ func LatencyQuantiles(device int, recs []TraceRecord, qPpm []uint32) ([3]Quantil
 	return res, nil
 }
 
+// DesArrivals returns the arrival times (ns since batch start) ServeUnderLoad
+// uses for traces [begin, begin+n) at the same mean gap (isim_des_arrivals).
+func (h *Handler) DesArrivals(device int, begin uint64, meanGapNs uint64, n int) ([]uint64, error) {
+	p := C.isim_des_params{mean_interarrival_ns: C.uint64_t(meanGapNs)}
+	out := make([]uint64, n)
+	rc := C.isim_des_arrivals(h.h, C.int(device), &p, C.uint64_t(begin), C.uint64_t(n), u64ptr(out))
+	return out, lastErr(rc)
+}
+
+// TimelineRow is one row of a timeline table: the requests that arrived in
+// the window and, of those that completed in it, by code (0: 200, 1: 500),
+// their count, latency sum, latency maximum and Prometheus histogram.
+type TimelineRow struct {
+	Arrived uint64
+	Done    [2]uint64
+	SumLat  [2]uint64
+	MaxLat  [2]uint64
+	Prom    [2][]uint64
+}
+
+// Timeline bins arrivals and records into nWindows windows of windowNs from
+// t0Ns on GPU `device` (isim_timeline).  Rows: "before" t0Ns, the windows,
+// "after" the last window.
+func Timeline(device int, arrivals []uint64, recs []TraceRecord, t0Ns, windowNs uint64, nWindows uint32) ([]TimelineRow, error) {
+	if len(arrivals) != len(recs) {
+		return nil, errors.New("arrivals and records differ in length")
+	}
+	p := C.isim_timeline_params{t0_ns: C.uint64_t(t0Ns), window_ns: C.uint64_t(windowNs), n_windows: C.uint32_t(nWindows)}
+	var rp *TraceRecord
+	if len(recs) > 0 {
+		rp = &recs[0]
+	}
+	if nWindows < 1 || nWindows > C.ISIM_TL_MAX_WINDOWS {
+		// libisim's EINVAL and message; the output is never written
+		return nil, lastErr(C.isim_timeline(C.int(device), u64ptr(arrivals), rp, C.uint64_t(len(recs)), &p, nil))
+	}
+	const w = C.ISIM_TL_ROW_WORDS
+	out := make([]uint64, (int(nWindows)+2)*w)
+	rc := C.isim_timeline(C.int(device), u64ptr(arrivals), rp, C.uint64_t(len(recs)), &p, u64ptr(out))
+	if rc != C.ISIM_OK {
+		return nil, lastErr(rc)
+	}
+	rows := make([]TimelineRow, int(nWindows)+2)
+	for i := range rows {
+		r := out[i*w : (i+1)*w]
+		rows[i].Arrived = r[C.ISIM_TL_ARRIVED]
+		for c := 0; c < 2; c++ {
+			rows[i].Done[c] = r[C.ISIM_TL_DONE+c]
+			rows[i].SumLat[c] = r[C.ISIM_TL_SUM_LAT+c]
+			rows[i].MaxLat[c] = r[C.ISIM_TL_MAX_LAT+c]
+			rows[i].Prom[c] = r[C.ISIM_TL_PROM+c*C.ISIM_N_PROM : C.ISIM_TL_PROM+(c+1)*C.ISIM_N_PROM]
+		}
+	}
+	return rows, nil
+}
+
 type Multi struct{ m *C.isim_multi }
 
 // u64ptr passes an empty slice as NULL (libisim then reports EINVAL) instead

@@ -499,6 +499,70 @@ ISIM_API int isim_latency_quantiles_device(const isim_trace_rec *d_records, uint
 ISIM_API int isim_latency_quantiles(int device, const isim_trace_rec *h_records, uint64_t n_records,
                                     const uint32_t *q_ppm, uint32_t n_q, uint64_t *h_out);  /* synchronous convenience */
 
+/* ---- the load-test timeline: arrival times and per-window latency ----
+ * A DES batch's time axis.  isim_des_arrivals* exports the arrival times the
+ * engine itself uses; isim_timeline* bins arrivals and records into windows of
+ * simulated time.  Both run on the device, asynchronously on the caller's
+ * stream: no host synchronisation, no allocation, graph-capturable from the
+ * first call.
+ *
+ * A[i] = arrival (ns since batch start) of trace trace_begin + i, exactly the
+ * value isim_serve_des* uses for the same handler seed, p->mean_interarrival_ns
+ * and trace_begin (A_t = sum of X_i, i = trace_begin .. t; the
+ * engine's own kernels).  Needs no DES plan: any handler, also one outside the
+ * DES class.  The workspace may be dirty.  n_traces 0: ISIM_OK, nothing
+ * written.  ISIM_EINVAL: a null h, p or arrivals buffer (n_traces > 0), a mean
+ * outside 1..2^34, a nonzero p->reserved or unknown p->flags
+ * (ISIM_DES_FLAG_WIDE is accepted and ignored), n_traces above 2^40, a
+ * workspace below isim_des_arrivals_workspace_bytes(n_traces) or not 8-byte
+ * aligned. */
+ISIM_API int isim_des_arrivals_workspace_bytes(uint64_t n_traces, uint64_t *bytes);   /* host only */
+ISIM_API int isim_des_arrivals_device(const isim_handler *h, const isim_des_params *p,
+                                      uint64_t trace_begin, uint64_t n_traces, uint64_t *d_arrivals,
+                                      void *d_workspace, uint64_t workspace_bytes, void *hip_stream);
+ISIM_API int isim_des_arrivals(const isim_handler *h, int device, const isim_des_params *p,
+                               uint64_t trace_begin, uint64_t n_traces, uint64_t *h_arrivals);
+
+/* Record i arrives at a = arrivals[i] and completes at c = a + latency_ns,
+ * saturating at 2^64 - 1.  A time x falls in row 0 ("before") if x < t0_ns;
+ * otherwise, with w = floor((x - t0_ns) / window_ns), in row 1 + w if
+ * w < n_windows, else in row n_windows + 1 ("after").  A time equal to a
+ * window's start belongs to that window; t0_ns + n_windows * window_ns is
+ * never formed.  The code is bit 31 of status_err, the histogram's bucket the
+ * one of ISIM_ST_PROM.  Exact integer arithmetic for every u64 input; the
+ * arrivals need not be sorted.  out is ACCUMULATED into, like d_stats (zero it
+ * first): sums and counts by add, ISIM_TL_MAX_LAT by max; so batches, shards
+ * and GPUs fold into one table, on the device by calling again and on the host
+ * with isim_timeline_merge.  Requests in flight at the end of window w:
+ * sum over rows r <= 1 + w (with "before") of ARRIVED - DONE[0] - DONE[1].
+ * n 0: ISIM_OK, nothing touched.  ISIM_EINVAL: a null p or out, null arrivals
+ * or records with n > 0, window_ns 0, n_windows 0 or above
+ * ISIM_TL_MAX_WINDOWS, a nonzero reserved, n above 2^40, records not 16-byte
+ * or arrivals / out not 8-byte aligned. */
+#define ISIM_TL_MAX_WINDOWS 65536u
+typedef struct {
+  uint64_t t0_ns;       /* start of window 0 */
+  uint64_t window_ns;   /* >= 1 */
+  uint32_t n_windows;   /* 1 .. ISIM_TL_MAX_WINDOWS */
+  uint32_t reserved;    /* 0 */
+} isim_timeline_params;
+
+/* Row words (u64), one row per window, preceded by row "before" (index 0) and
+ * followed by row "after" (index n_windows + 1): out[(n_windows + 2)][ISIM_TL_ROW_WORDS] */
+#define ISIM_TL_ARRIVED  0                       /* records whose ARRIVAL falls in the window */
+#define ISIM_TL_DONE     1                       /* [2] records whose COMPLETION falls in it, by code 200|500 */
+#define ISIM_TL_SUM_LAT  3                       /* [2] sum of latency_ns of those, by code */
+#define ISIM_TL_MAX_LAT  5                       /* [2] max latency_ns of those, by code */
+#define ISIM_TL_PROM     7                       /* [2][ISIM_N_PROM] latency histogram of those, the stats buffer's edges */
+#define ISIM_TL_ROW_WORDS (7 + 2 * ISIM_N_PROM)  /* 73 */
+
+ISIM_API int isim_timeline_device(const uint64_t *d_arrivals, const isim_trace_rec *d_records, uint64_t n,
+                                  const isim_timeline_params *p, uint64_t *d_out, void *hip_stream);
+/* Synchronous convenience: host buffers; h_out is accumulated into as well. */
+ISIM_API int isim_timeline(int device, const uint64_t *h_arrivals, const isim_trace_rec *h_records, uint64_t n,
+                           const isim_timeline_params *p, uint64_t *h_out);
+ISIM_API int isim_timeline_merge(uint32_t n_windows, uint64_t *dst, const uint64_t *src);  /* host: SUM, MAX words by MAX */
+
 #ifdef __cplusplus
 }
 #endif

@@ -1198,6 +1198,72 @@ int isim_serve_des(isim_handler *h, int device, const isim_des_params *dp, uint6
   return rc;
 }
 
+// ---- the arrival times alone (the engine's kernels, des.hip des_arrivals_launch)
+static uint64_t des_arrivals_ws_bytes(uint64_t n) { return ((isim::des_arrivals_blocks(n) + 1) * 8 + 255) & ~255ull; }
+
+static int des_arrivals_check(const isim_handler *h, const isim_des_params *dp, uint64_t n_traces, const void *out) {
+  if (!h || !dp) return fail(ISIM_EINVAL, "null argument");
+  if (dp->mean_interarrival_ns == 0 || dp->mean_interarrival_ns > (1ull << 34))
+    return fail(ISIM_EINVAL, "mean_interarrival_ns must be in [1, 2^34]");
+  if (dp->reserved != 0 || (dp->flags & ~ISIM_DES_FLAG_WIDE) != 0)
+    return fail(ISIM_EINVAL, "isim_des_params.flags must be 0 or ISIM_DES_FLAG_WIDE, reserved 0");
+  if (n_traces > (1ull << 40)) return fail(ISIM_EINVAL, "n_traces above 2^40");
+  if (n_traces && !out) return fail(ISIM_EINVAL, "null arrivals buffer");
+  return ISIM_OK;
+}
+
+int isim_des_arrivals_workspace_bytes(uint64_t n_traces, uint64_t *bytes) {
+  if (!bytes) return fail(ISIM_EINVAL, "null argument");
+  if (n_traces > (1ull << 40)) return fail(ISIM_EINVAL, "n_traces above 2^40");
+  *bytes = des_arrivals_ws_bytes(n_traces);
+  return ISIM_OK;
+}
+
+int isim_des_arrivals_device(const isim_handler *h, const isim_des_params *dp, uint64_t trace_begin,
+                             uint64_t n_traces, uint64_t *d_arrivals, void *d_workspace, uint64_t workspace_bytes,
+                             void *hip_stream) {
+  if (const int rc = des_arrivals_check(h, dp, n_traces, d_arrivals)) return rc;
+  if (n_traces == 0) return ISIM_OK;
+  if (!d_workspace || workspace_bytes < des_arrivals_ws_bytes(n_traces))
+    return fail(ISIM_EINVAL, "arrivals workspace smaller than isim_des_arrivals_workspace_bytes()");
+  if (((uintptr_t)d_arrivals & 7u) || ((uintptr_t)d_workspace & 7u))
+    return fail(ISIM_EINVAL, "d_arrivals and d_workspace must be 8-byte aligned");
+  if (isim::des_arrivals_launch(h->params.seed, dp->mean_interarrival_ns, trace_begin, n_traces, d_arrivals,
+                                (uint64_t *)d_workspace, hip_stream) != 0)
+    return fail(ISIM_EHIP, "arrivals kernel launch failed");
+  return ISIM_OK;
+}
+
+int isim_des_arrivals(const isim_handler *h, int device, const isim_des_params *dp, uint64_t trace_begin,
+                      uint64_t n_traces, uint64_t *h_arrivals) {
+  if (const int rc = des_arrivals_check(h, dp, n_traces, h_arrivals)) return rc;
+  if (n_traces == 0) return ISIM_OK;
+  int prev = 0;
+  HIPCHK(hipGetDevice(&prev));
+  HIPCHK(hipSetDevice(device));
+  const uint64_t ws_bytes = des_arrivals_ws_bytes(n_traces);
+  void *d_a = nullptr, *d_ws = nullptr;
+  hipStream_t s = nullptr;
+  int rc = ISIM_OK;
+  do {
+    if (hipStreamCreate(&s) != hipSuccess || hipMalloc(&d_a, n_traces * 8) != hipSuccess ||
+        hipMalloc(&d_ws, ws_bytes) != hipSuccess) {
+      rc = fail(ISIM_EHIP, "hipMalloc(arrivals buffers) failed");
+      break;
+    }
+    rc = isim_des_arrivals_device(h, dp, trace_begin, n_traces, (uint64_t *)d_a, d_ws, ws_bytes, s);
+    if (rc != ISIM_OK) break;
+    if (hipMemcpyAsync(h_arrivals, d_a, n_traces * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      rc = fail(ISIM_EHIP, "copy arrivals failed");
+  } while (0);
+  (void)hipFree(d_a);
+  (void)hipFree(d_ws);
+  if (s) (void)hipStreamDestroy(s);
+  (void)hipSetDevice(prev);
+  return rc;
+}
+
 void isim_debug_set_spin_limit(uint32_t polls) { isim::des_set_spin_limit(polls); }
 
 uint32_t isim_debug_spin_limit(void) { return isim::des_spin_limit(); }

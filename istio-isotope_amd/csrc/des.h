@@ -208,6 +208,12 @@ uint64_t des_workspace_bytes(const DesPlan &plan, uint64_t n, uint64_t stats_wor
 // Points L's workspace parts into `workspace` (L.plan, n_traces, stats_words, table_rows set).
 void des_carve(DesLaunch &L, void *workspace);
 int des_launch(const DesLaunch &L, void *stream);
+// The arrivals alone, by the engine's own kernels (isim_des_arrivals*): A[i]
+// of trace trace_begin + i into d_arrivals[n]; d_blk holds
+// des_arrivals_blocks(n) + 1 chunk sums and may be dirty.  0 or 1 (HIP error).
+uint64_t des_arrivals_blocks(uint64_t n);
+int des_arrivals_launch(uint64_t seed, uint64_t mean_ns, uint64_t trace_begin, uint64_t n, uint64_t *d_arrivals,
+                        uint64_t *d_blk, void *stream);
 // Polls a decoupled look-back (des.hip chain pass, pipelined pass; des_items.hip
 // k_qscan) makes for a predecessor before it gives up and FAILS the batch (a
 // device fault flag: the batch is not accumulated and the call reports it).

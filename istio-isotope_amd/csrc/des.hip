@@ -48,6 +48,7 @@
 #define ISIM_NT_ROWS 1  // row stores of fused leaves and finishes nontemporal: keep L2 for the A_t re-reads
 #endif
 #include "kernel_abi.h"
+#include "des_bucket.h"
 
 namespace isim {
 void *stream_calls_kernel();
@@ -134,47 +135,6 @@ __device__ __forceinline__ uint64_t des_exp_q24(uint32_t u) {
   const uint32_t idx = f >> 16, rem = f & 0xFFFFu;
   const int64_t lnm = c_ln[idx] + ((((int64_t)c_ln[idx + 1] - c_ln[idx]) * (int64_t)rem) >> 16);
   return (uint64_t)(24 * kLn2Q24 - ((int64_t)e * kLn2Q24 + lnm));
-}
-
-// Prometheus duration bucket (prometheus/handler.go:26-35): the first edge
-// >= t.  The edges are whole milliseconds in six arithmetic runs (7..12 by 1,
-// 14..20 by 2, 25..50 by 5, 60..100 by 10, 120..200 by 20, 250..500 by 50), so
-// with m = ceil(t / 1 ms) (t <= e ms  <=>  m <= e) the bucket is the run's
-// base + ceil((m - run start) / step).  The kernels look m up in a 501-byte
-// LDS table built from this formula (des_bucket_lut: 7 VALU per duration
-// instead of 57).
-__host__ __device__ constexpr uint32_t des_prom_bucket_m(uint32_t m) {
-  const uint32_t lo = m <= 12 ? 7 : m <= 20 ? 12 : m <= 50 ? 20 : m <= 100 ? 50 : m <= 200 ? 100 : 200;
-  const uint32_t base = m <= 12 ? 0 : m <= 20 ? 5 : m <= 50 ? 9 : m <= 100 ? 15 : m <= 200 ? 20 : 25;
-  const uint32_t d = m <= 12 ? 1 : m <= 20 ? 2 : m <= 50 ? 5 : m <= 100 ? 10 : m <= 200 ? 20 : 50;
-  // ceil(65536 / d): exact quotients for numerators below 2^9
-  const uint32_t M = m <= 12 ? 65536 : m <= 20 ? 32768 : m <= 50 ? 13108 : m <= 100 ? 6554 : m <= 200 ? 3277 : 1311;
-  const uint32_t n = m > lo ? m - lo : 0;
-  return base + (((n + d - 1) * M) >> 16);
-}
-constexpr uint32_t kBucketLut = 502;  // m = ceil(t / 1 ms) in 0..500; 501: above 500 ms (+Inf)
-constexpr uint32_t kBucketLutWords = 128;
-struct DesBucketLut {
-  uint32_t w[kBucketLutWords];  // byte m of the table: the bucket of m (m <= 501), little-endian
-  constexpr DesBucketLut() : w() {
-    for (uint32_t m = 0; m < 4 * kBucketLutWords; ++m)
-      w[m / 4] |= (m < kBucketLut ? des_prom_bucket_m(m) : 32u) << (8 * (m % 4));
-  }
-};
-__device__ constexpr DesBucketLut kDesBucketLut{};
-// copies the table into the workgroup's LDS (the caller's barrier publishes
-// it): one 4-byte word per thread instead of computing 502 entries
-__device__ __forceinline__ void des_bucket_lut_init(uint8_t *lut) {
-  for (uint32_t i = threadIdx.x; i < kBucketLutWords; i += blockDim.x)
-    reinterpret_cast<uint32_t *>(lut)[i] = kDesBucketLut.w[i];
-}
-__device__ __forceinline__ uint32_t des_prom_bucket32(const uint8_t *lut, uint32_t t) {
-  const uint32_t c = t < 500000001u ? t : 500000001u;  // v_min_u32
-  return lut[(c + 999999u) / 1000000u];
-}
-__device__ __forceinline__ uint32_t des_prom_bucket(const uint8_t *lut, uint64_t t) {
-  const uint32_t c = (uint32_t)(t < 500000001ull ? t : 500000001ull);  // branch-free: entry 501 is the +Inf bucket
-  return lut[(c + 999999u) / 1000000u];
 }
 
 struct ChainState;
@@ -2598,6 +2558,32 @@ static std::atomic<uint32_t> g_spin_limit{kDesSpinLimit};
 uint32_t des_spin_limit() { return g_spin_limit.load(std::memory_order_relaxed); }
 void des_set_spin_limit(uint32_t polls) { g_spin_limit.store(polls, std::memory_order_relaxed); }
 
+// A[t] of the batch k describes (N, trace_begin, mean_ns, k0, k1, A, blk,
+// n_blk): the chunk prefixes, the scan of the chunk sums, the offsets added
+static void launch_arrivals(const dev::DesK &k, hipStream_t stream) {
+  using namespace dev;
+  hipLaunchKernelGGL(des_arrivals, dim3(k.n_blk), dim3(kDesThreads), 0, stream, k);
+  hipLaunchKernelGGL(des_scan_blocks, dim3(1), dim3(kDesThreads), 0, stream, k);
+  hipLaunchKernelGGL(des_add_blocks, dim3(k.n_blk), dim3(kDesThreads), 0, stream, k);
+}
+
+uint64_t des_arrivals_blocks(uint64_t n) { return (n + dev::kDesChunk - 1) / dev::kDesChunk; }
+
+int des_arrivals_launch(uint64_t seed, uint64_t mean_ns, uint64_t trace_begin, uint64_t n, uint64_t *d_arrivals,
+                        uint64_t *d_blk, void *stream) {
+  dev::DesK k{};
+  k.A = d_arrivals;
+  k.blk = d_blk;
+  k.N = n;
+  k.trace_begin = trace_begin;
+  k.mean_ns = mean_ns;
+  k.k0 = (uint32_t)seed;
+  k.k1 = (uint32_t)(seed >> 32);
+  k.n_blk = (uint32_t)des_arrivals_blocks(n);
+  launch_arrivals(k, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 int des_launch(const DesLaunch &L, void *stream_) {
   using namespace dev;
   hipStream_t stream = (hipStream_t)stream_;
@@ -2641,9 +2627,7 @@ int des_launch(const DesLaunch &L, void *stream_) {
   if (hipMemsetAsync(B.E, 0, L.n_traces * sizeof(uint32_t), stream) != hipSuccess) return 1;
   if (hipMemsetAsync(B.ovf, 0, 8, stream) != hipSuccess) return 1;  // overflow flag + changed flag
   if (hipMemsetAsync(B.stage, 0, (L.stats_words + table_words) * 8, stream) != hipSuccess) return 1;
-  hipLaunchKernelGGL(des_arrivals, dim3(k.n_blk), dim3(kDesThreads), 0, stream, k);
-  hipLaunchKernelGGL(des_scan_blocks, dim3(1), dim3(kDesThreads), 0, stream, k);
-  hipLaunchKernelGGL(des_add_blocks, dim3(k.n_blk), dim3(kDesThreads), 0, stream, k);
+  launch_arrivals(k, stream);
   {
     const uint64_t threads = (uint64_t)((L.n_pos + 3) / 4) * k.st_wpr;
     hipLaunchKernelGGL(des_status, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, k);

@@ -12,3 +12,5 @@ from . import prometheus  # noqa: F401
 from .des import DesHandler  # noqa: F401
 from .quantiles import (DEFAULT_Q, latency_quantiles, latency_quantiles_device, quantile_rank,  # noqa: F401
                         quantiles_out_words, quantiles_workspace_bytes)
+from .timeline import (decode_timeline, des_arrivals, des_arrivals_device, des_arrivals_workspace_bytes,  # noqa: F401
+                       timeline, timeline_device, timeline_merge, timeline_out_words, timeline_table)

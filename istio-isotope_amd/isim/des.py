@@ -74,6 +74,19 @@ class DesHandler:
             self.handler._h, C.byref(p), trace_begin, n_traces, d_records or None, d_stats, d_table,
             d_workspace, workspace_bytes, stream or None))
 
+    def arrivals(self, trace_begin: int, n_traces: int, device: int = 0) -> np.ndarray:
+        """The arrival times (u64 ns since batch start) `serve` uses for these traces."""
+        from .timeline import des_arrivals
+        return des_arrivals(self.handler, self.params.mean_interarrival_ns, trace_begin, n_traces, device)
+
+    def timeline(self, trace_begin: int, n_traces: int, window_ns: int, n_windows: int, t0_ns: int = 0,
+                 device: int = 0) -> dict:
+        """Serves the batch (as `serve`: wide rows on retry) and bins it into
+        windows of simulated time: isim.timeline of its arrivals and records."""
+        from .timeline import timeline
+        recs, _, _ = self.serve(trace_begin, n_traces, device)
+        return timeline(self.arrivals(trace_begin, n_traces, device), recs, window_ns, n_windows, t0_ns, device)
+
     def fold(self, table: np.ndarray) -> np.ndarray:
         n = self.handler.info.n_services
         out = np.zeros((max(1, n), native.DES_ROW_WORDS), np.uint64)

@@ -54,6 +54,10 @@ DES_FLAG_WIDE = 1  # isim_des_params.flags: 64-bit rows
 # exact latency percentiles (isim.h ISIM_Q_*): out is u64[3][1 + n_q], per class the count then the values
 MAX_QUANTILES = 16
 Q_ALL, Q_200, Q_500 = 0, 1, 2
+# the load-test timeline (isim.h ISIM_TL_*): out is u64[n_windows + 2][TL_ROW_WORDS], rows "before", windows, "after"
+TL_MAX_WINDOWS = 65536
+TL_ARRIVED, TL_DONE, TL_SUM_LAT, TL_MAX_LAT, TL_PROM = 0, 1, 3, 5, 7
+TL_ROW_WORDS = 7 + 2 * N_PROM
 
 
 class IsimError(RuntimeError):
@@ -91,6 +95,10 @@ class LaunchInfo(C.Structure):
 
 class DesParams(C.Structure):
     _fields_ = [("mean_interarrival_ns", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TimelineParams(C.Structure):
+    _fields_ = [("t0_ns", C.c_uint64), ("window_ns", C.c_uint64), ("n_windows", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class K8sParams(C.Structure):
@@ -167,6 +175,13 @@ SIGNATURES = {
     "isim_latency_quantiles_device": (C.c_int, [_VP, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, _VP, _VP,
                                                 C.c_uint64, _VP]),
     "isim_latency_quantiles": (C.c_int, [C.c_int, _VP, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, _VP]),
+    "isim_des_arrivals_workspace_bytes": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "isim_des_arrivals_device": (C.c_int, [_VP, C.POINTER(DesParams), C.c_uint64, C.c_uint64, _VP, _VP, C.c_uint64,
+                                           _VP]),
+    "isim_des_arrivals": (C.c_int, [_VP, C.c_int, C.POINTER(DesParams), C.c_uint64, C.c_uint64, _VP]),
+    "isim_timeline_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(TimelineParams), _VP, _VP]),
+    "isim_timeline": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, C.POINTER(TimelineParams), _VP]),
+    "isim_timeline_merge": (C.c_int, [C.c_uint32, _VP, _VP]),
 }
 
 _lib = None
