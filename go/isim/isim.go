@@ -250,6 +250,45 @@ func Timeline(device int, arrivals []uint64, recs []TraceRecord, t0Ns, windowNs 
 	return rows, nil
 }
 
+// TimelineQuantiles computes, for every row of the Timeline table ("before"
+// t0Ns, the nWindows windows of windowNs, "after" the last), the exact
+// latency percentiles of the records that complete in it on GPU `device`
+// (isim_timeline_quantiles): per row the classes of LatencyQuantiles
+// (C.ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500).  qPpm as in LatencyQuantiles.
+func TimelineQuantiles(device int, arrivals []uint64, recs []TraceRecord, t0Ns, windowNs uint64, nWindows uint32, qPpm []uint32) ([][3]Quantiles, error) {
+	if len(arrivals) != len(recs) {
+		return nil, errors.New("arrivals and records differ in length")
+	}
+	p := C.isim_timeline_params{t0_ns: C.uint64_t(t0Ns), window_ns: C.uint64_t(windowNs), n_windows: C.uint32_t(nWindows)}
+	var rp *TraceRecord
+	if len(recs) > 0 {
+		rp = &recs[0]
+	}
+	var qp *C.uint32_t
+	if len(qPpm) > 0 {
+		qp = (*C.uint32_t)(unsafe.Pointer(&qPpm[0]))
+	}
+	nq := len(qPpm)
+	if nWindows < 1 || nWindows > C.ISIM_TL_MAX_WINDOWS || nq < 1 || nq > C.ISIM_MAX_QUANTILES {
+		// libisim's EINVAL and message; the output is never written
+		return nil, lastErr(C.isim_timeline_quantiles(C.int(device), u64ptr(arrivals), rp, C.uint64_t(len(recs)), &p, qp, C.uint32_t(nq), nil))
+	}
+	w := 3 * (1 + nq) // ISIM_Q_OUT_WORDS per row: ISIM_TLQ_OUT_WORDS (cgo sees no function-like macros)
+	out := make([]uint64, (int(nWindows)+2)*w)
+	rc := C.isim_timeline_quantiles(C.int(device), u64ptr(arrivals), rp, C.uint64_t(len(recs)), &p, qp, C.uint32_t(nq), u64ptr(out))
+	if rc != C.ISIM_OK {
+		return nil, lastErr(rc)
+	}
+	rows := make([][3]Quantiles, int(nWindows)+2)
+	for i := range rows {
+		for c := 0; c < 3; c++ {
+			r := out[i*w+c*(1+nq) : i*w+(c+1)*(1+nq)]
+			rows[i][c] = Quantiles{Count: r[0], Values: r[1:]}
+		}
+	}
+	return rows, nil
+}
+
 type Multi struct{ m *C.isim_multi }
 
 // u64ptr passes an empty slice as NULL (libisim then reports EINVAL) instead

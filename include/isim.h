@@ -563,6 +563,43 @@ ISIM_API int isim_timeline(int device, const uint64_t *h_arrivals, const isim_tr
                            const isim_timeline_params *p, uint64_t *h_out);
 ISIM_API int isim_timeline_merge(uint32_t n_windows, uint64_t *dst, const uint64_t *src);  /* host: SUM, MAX words by MAX */
 
+/* ---- per-window exact latency percentiles: p99 over time ----
+ * For every row of the timeline above (the same isim_timeline_params, the
+ * same rules for them, the same rows), the exact order statistics of the
+ * latencies that COMPLETE in it (c = arrivals[i] + latency_ns, saturating), by
+ * the classes of isim_latency_quantiles (ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500,
+ * bit 31 of status_err).  out is u64[n_windows + 2][3][1 + n_q]: out[r][c][0]
+ * is the count N of records of class c completing in row r, out[r][c][1 + i]
+ * the k-th smallest latency_ns among them, k = isim_quantile_rank(N, q_ppm[i])
+ * (nearest rank); all 0 where N is 0.  Unlike the timeline table, out is
+ * WRITTEN, not accumulated (order statistics do not merge): every word is
+ * written by the call, so out may be dirty; n 0 writes all zeros; to cover
+ * several batches pass their concatenated arrivals and records.  Any u64
+ * latency is valid, the arrivals need not be sorted; q_ppm is a host array
+ * copied at the call, 1 .. ISIM_MAX_QUANTILES entries, each <= 1,000,000, in
+ * any order, repeats allowed.
+ * n is at most 2^32 - 1: the call needs 8 B of workspace per record (the
+ * latencies, grouped by row) and its per-row counters, offsets and ranks are
+ * 32-bit.  ISIM_EINVAL, before any HIP call: the parameter errors of
+ * isim_timeline*, the quantile-list errors of isim_latency_quantiles*, n above
+ * 2^32 - 1, a null out or workspace, null arrivals or records with n > 0,
+ * records not 16-byte or arrivals / out / workspace not 8-byte aligned, a
+ * workspace below isim_timeline_quantiles_workspace_bytes(n, n_windows, n_q).
+ * The device entry keeps the contract of isim_latency_quantiles_device:
+ * asynchronous on hip_stream, no host synchronisation, no allocation,
+ * graph-capturable from the first call; the workspace may be dirty, and calls
+ * that share one must be ordered (e.g. on one stream). */
+#define ISIM_TLQ_OUT_WORDS(n_windows, n_q) (((uint64_t)(n_windows) + 2) * ISIM_Q_OUT_WORDS(n_q))
+ISIM_API int isim_timeline_quantiles_workspace_bytes(uint64_t n, uint32_t n_windows, uint32_t n_q,
+                                                     uint64_t *bytes);               /* host only */
+ISIM_API int isim_timeline_quantiles_device(const uint64_t *d_arrivals, const isim_trace_rec *d_records, uint64_t n,
+                                            const isim_timeline_params *p, const uint32_t *q_ppm, uint32_t n_q,
+                                            uint64_t *d_out, void *d_workspace, uint64_t workspace_bytes,
+                                            void *hip_stream);
+ISIM_API int isim_timeline_quantiles(int device, const uint64_t *h_arrivals, const isim_trace_rec *h_records,
+                                     uint64_t n, const isim_timeline_params *p, const uint32_t *q_ppm, uint32_t n_q,
+                                     uint64_t *h_out);                               /* synchronous convenience */
+
 #ifdef __cplusplus
 }
 #endif

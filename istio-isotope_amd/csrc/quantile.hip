@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/isim.h"
+#include "quantile_rank.h"
 
 namespace isim {
 int set_error(int code, const std::string &msg);  // api.hip
@@ -58,11 +59,7 @@ constexpr uint64_t kStateBytes = (sizeof(QState) + 255) & ~255ull;
 
 uint64_t workspace_bytes(uint32_t n_q) { return kStateBytes + (uint64_t)kClasses * n_q * kBins * 8; }
 
-__host__ __device__ inline uint64_t nearest_rank(uint64_t n, uint32_t q_ppm) {
-  // n <= 2^40, q_ppm <= 10^6 < 2^20: the product stays below 2^60
-  const uint64_t k = (n * (uint64_t)q_ppm + 999999ull) / 1000000ull;
-  return k ? k : 1;
-}
+using isim::q::nearest_rank;  // quantile_rank.h
 
 // Zeroes the workspace the select uses (the caller may hand over a dirty one),
 // or the output of an empty batch.  A kernel like the rest of the sequence, so
@@ -275,10 +272,7 @@ __global__ __launch_bounds__(kResolveThreads) void k_quantile_resolve(QState *st
 }
 
 int check_q(const uint32_t *q_ppm, uint32_t n_q, uint64_t n_records) {
-  if (n_q == 0 || n_q > kMaxQ) return qfail("n_q must be 1.." + std::to_string(kMaxQ));
-  if (!q_ppm) return qfail("null q_ppm");
-  for (uint32_t i = 0; i < n_q; ++i)
-    if (q_ppm[i] > 1000000u) return qfail("q_ppm[" + std::to_string(i) + "] is above 1000000");
+  if (const std::string m = isim::q::list_error(q_ppm, n_q); !m.empty()) return qfail(m);
   if (n_records > kMaxRecords) return qfail("n_records is above 2^40");
   return ISIM_OK;
 }

@@ -23,6 +23,7 @@
 
 #include "../../include/isim.h"
 #include "des_bucket.h"
+#include "timeline_row.h"
 
 namespace isim {
 int set_error(int code, const std::string &msg);  // api.hip
@@ -64,35 +65,8 @@ struct TlArgs {
   uint32_t pow2;
 };
 
-// floor(x / d) for every u64 x with m = floor((2^64 - 1) / d): the estimate
-// q' = mulhi(x, m) satisfies x/d - 1 < x m / 2^64 <= x/d (m >= (2^64 - d) / d
-// and x < 2^64), so q' is q or q - 1 and the remainder x - q' d lies in
-// [0, 2 d): one correction (the second never fires; it costs two VALU).
-__host__ __device__ inline uint64_t mulhi64(uint64_t a, uint64_t b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __umul64hi(a, b);
-#else
-  return (uint64_t)(((unsigned __int128)a * b) >> 64);
-#endif
-}
-__host__ __device__ inline uint64_t div_recip(uint64_t x, uint64_t d, uint64_t m) {
-  uint64_t q = mulhi64(x, m);
-  uint64_t r = x - q * d;
-  if (r >= d) {
-    ++q;
-    r -= d;
-  }
-  if (r >= d) ++q;
-  return q;
-}
-
-// the table row of time x: 0 before t0, 1 + w for window w, n_windows + 1 after the last
-__device__ __forceinline__ uint32_t tl_row(const TlArgs &a, uint64_t x) {
-  if (x < a.t0) return 0u;
-  const uint64_t d = x - a.t0;
-  const uint64_t w = a.pow2 ? d >> a.shift : div_recip(d, a.window, a.recip);
-  return 1u + (uint32_t)(w < a.n_windows ? w : a.n_windows);
-}
+// the table row of time x (timeline_row.h)
+__device__ __forceinline__ uint32_t tl_row(const TlArgs &a, uint64_t x) { return isim::tl::row_of(a, x); }
 
 // ---- wave reductions (all 64 lanes active): row shifts, then the row totals
 // broadcast into the later rows; lane 63 holds the result.  0 is the identity
@@ -260,11 +234,7 @@ __global__ __launch_bounds__(kThreads) void k_timeline(TlArgs a) {
 }
 
 int check_params(const isim_timeline_params *p, uint64_t n) {
-  if (!p) return tfail("null isim_timeline_params");
-  if (p->window_ns == 0) return tfail("window_ns must be at least 1");
-  if (p->n_windows == 0 || p->n_windows > ISIM_TL_MAX_WINDOWS)
-    return tfail("n_windows must be 1.." + std::to_string(ISIM_TL_MAX_WINDOWS));
-  if (p->reserved != 0) return tfail("isim_timeline_params.reserved must be 0");
+  if (const char *m = isim::tl::params_error(p)) return tfail(m);
   if (n > kMaxRecords) return tfail("n is above 2^40");
   return ISIM_OK;
 }
@@ -288,12 +258,7 @@ int isim_timeline_device(const uint64_t *d_arrivals, const isim_trace_rec *d_rec
   a.rec = (const rec4 *)d_records;
   a.out = (unsigned long long *)d_out;
   a.n = n;
-  a.t0 = p->t0_ns;
-  a.window = p->window_ns;
-  a.recip = ~0ull / p->window_ns;
-  a.n_windows = p->n_windows;
-  a.pow2 = (p->window_ns & (p->window_ns - 1)) == 0 ? 1u : 0u;
-  a.shift = a.pow2 ? (uint32_t)__builtin_ctzll(p->window_ns) : 0u;
+  isim::tl::set_row_args(a, *p);
   const uint64_t grid = (n + kTile - 1) / kTile;  // n <= 2^40: at most 2^28 workgroups
   hipLaunchKernelGGL(k_timeline, dim3((uint32_t)grid), dim3(kThreads), 0, (hipStream_t)hip_stream, a);
   THIPCHK(hipGetLastError());

@@ -14,3 +14,6 @@ from .quantiles import (DEFAULT_Q, latency_quantiles, latency_quantiles_device, 
                         quantiles_out_words, quantiles_workspace_bytes)
 from .timeline import (decode_timeline, des_arrivals, des_arrivals_device, des_arrivals_workspace_bytes,  # noqa: F401
                        timeline, timeline_device, timeline_merge, timeline_out_words, timeline_table)
+from .timeline_quantiles import (decode_timeline_quantiles, timeline_quantiles, timeline_quantiles_device,  # noqa: F401
+                                 timeline_quantiles_out_words, timeline_quantiles_table,
+                                 timeline_quantiles_workspace_bytes)

@@ -24,6 +24,7 @@ import ctypes as C
 import numpy as np
 
 from . import native
+from .quantiles import DEFAULT_Q
 from .sim import REC_DTYPE, Handler
 
 
@@ -86,6 +87,15 @@ class DesHandler:
         from .timeline import timeline
         recs, _, _ = self.serve(trace_begin, n_traces, device)
         return timeline(self.arrivals(trace_begin, n_traces, device), recs, window_ns, n_windows, t0_ns, device)
+
+    def timeline_quantiles(self, trace_begin: int, n_traces: int, window_ns: int, n_windows: int, t0_ns: int = 0,
+                           q=DEFAULT_Q, device: int = 0) -> dict:
+        """Serves the batch (as `serve`) and gives the exact latency percentiles of what
+        completes in each window: isim.timeline_quantiles of its arrivals and records."""
+        from .timeline_quantiles import timeline_quantiles
+        recs, _, _ = self.serve(trace_begin, n_traces, device)
+        return timeline_quantiles(self.arrivals(trace_begin, n_traces, device), recs, window_ns, n_windows, t0_ns,
+                                  q, device)
 
     def fold(self, table: np.ndarray) -> np.ndarray:
         n = self.handler.info.n_services

@@ -182,6 +182,11 @@ SIGNATURES = {
     "isim_timeline_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(TimelineParams), _VP, _VP]),
     "isim_timeline": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, C.POINTER(TimelineParams), _VP]),
     "isim_timeline_merge": (C.c_int, [C.c_uint32, _VP, _VP]),
+    "isim_timeline_quantiles_workspace_bytes": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "isim_timeline_quantiles_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(TimelineParams), C.POINTER(C.c_uint32),
+                                                 C.c_uint32, _VP, _VP, C.c_uint64, _VP]),
+    "isim_timeline_quantiles": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, C.POINTER(TimelineParams),
+                                          C.POINTER(C.c_uint32), C.c_uint32, _VP]),
 }
 
 _lib = None
