@@ -19,6 +19,7 @@
 #include "k8s.h"
 #include "marshal.h"
 #include "des.h"
+#include "host_stage.h"
 #include "kernel_abi.h"
 #include "program.h"
 
@@ -1238,30 +1239,14 @@ int isim_des_arrivals(const isim_handler *h, int device, const isim_des_params *
                       uint64_t n_traces, uint64_t *h_arrivals) {
   if (const int rc = des_arrivals_check(h, dp, n_traces, h_arrivals)) return rc;
   if (n_traces == 0) return ISIM_OK;
-  int prev = 0;
-  HIPCHK(hipGetDevice(&prev));
-  HIPCHK(hipSetDevice(device));
   const uint64_t ws_bytes = des_arrivals_ws_bytes(n_traces);
-  void *d_a = nullptr, *d_ws = nullptr;
-  hipStream_t s = nullptr;
-  int rc = ISIM_OK;
-  do {
-    if (hipStreamCreate(&s) != hipSuccess || hipMalloc(&d_a, n_traces * 8) != hipSuccess ||
-        hipMalloc(&d_ws, ws_bytes) != hipSuccess) {
-      rc = fail(ISIM_EHIP, "hipMalloc(arrivals buffers) failed");
-      break;
-    }
-    rc = isim_des_arrivals_device(h, dp, trace_begin, n_traces, (uint64_t *)d_a, d_ws, ws_bytes, s);
-    if (rc != ISIM_OK) break;
-    if (hipMemcpyAsync(h_arrivals, d_a, n_traces * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      rc = fail(ISIM_EHIP, "copy arrivals failed");
-  } while (0);
-  (void)hipFree(d_a);
-  (void)hipFree(d_ws);
-  if (s) (void)hipStreamDestroy(s);
-  (void)hipSetDevice(prev);
-  return rc;
+  isim::HostStage stage(device);
+  void *d_a = stage.alloc(n_traces * 8), *d_ws = stage.alloc(ws_bytes);
+  if (stage.rc() != ISIM_OK) return stage.rc();
+  if (const int rc = isim_des_arrivals_device(h, dp, trace_begin, n_traces, (uint64_t *)d_a, d_ws, ws_bytes,
+                                              stage.stream()))
+    return rc;
+  return stage.download(h_arrivals, d_a, n_traces * 8);
 }
 
 void isim_debug_set_spin_limit(uint32_t polls) { isim::des_set_spin_limit(polls); }

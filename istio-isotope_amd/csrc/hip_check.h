@@ -1,0 +1,20 @@
+// Error reporting of the C-ABI translation units outside api.hip: the
+// thread's message (isim_last_error) and the check of a HIP call.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/isim.h"
+
+namespace isim {
+int set_error(int code, const std::string &msg);  // api.hip
+}
+
+// returns ISIM_EHIP from the calling function when a HIP call fails
+#define ISIM_HIPCHK(expr)                                                                          \
+  do {                                                                                             \
+    hipError_t e_ = (expr);                                                                        \
+    if (e_ != hipSuccess) return isim::set_error(ISIM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)

@@ -10,17 +10,19 @@
 #include <string>
 
 #include "../../include/isim.h"
+#include "host_stage.h"
 #include "quantile_rank.h"
-
-namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-}
+#include "radix_select.h"
+#include "trace_rec_dev.h"
 
 namespace {
 
-constexpr uint32_t kMaxQ = ISIM_MAX_QUANTILES;
-constexpr uint32_t kClasses = 3;
-constexpr uint32_t kBins = 256;
+namespace rs = isim::rs;
+using isim::dev::rec4;
+using rs::kBins;
+using rs::kClasses;
+using rs::kMaxQ;
+
 constexpr uint32_t kHistThreads = 512;  // 3 workgroups of 48 KB LDS per CU: 24 waves
 constexpr uint32_t kHistMaxGrid = 768;  // 3 per CU; a workgroup's u32 LDS bins hold 2^40 / 768 < 2^32 records
 constexpr uint32_t kUnroll = 4;         // records per lane in flight
@@ -29,33 +31,21 @@ constexpr uint64_t kMaxRecords = 1ull << 40;
 
 int qfail(const std::string &msg) { return isim::set_error(ISIM_EINVAL, msg); }
 
-#define QHIPCHK(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return isim::set_error(ISIM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-// The select's state, at the start of the workspace; the u64 histogram
-// [3][n_q][256] follows it.  A group is one still-distinct prefix of a class:
-// quantiles that share a prefix share a histogram.
+// The select's state (radix_select.h), at the start of the workspace; the u64
+// histogram [3][n_q][256] follows it.
 struct QState {
-  uint64_t cnt[kClasses];           // records per class (cnt[0] = n)
-  uint64_t any;                     // OR of every latency: the bytes above its top bit are zero
-  int32_t top_byte;                 // most significant byte with a set bit; -1: every latency is 0
-  uint32_t ngrp[kClasses];          // groups per class (0: the class is empty)
-  uint64_t gprefix[kClasses][kMaxQ];  // per group: the digits chosen so far
-  uint64_t prefix[kClasses][kMaxQ];   // per quantile: the digits chosen so far
-  uint64_t k[kClasses][kMaxQ];        // per quantile: 1-based rank among the records under its prefix
-  uint32_t grp[kClasses][kMaxQ];      // per quantile: its group
+  uint64_t cnt[kClasses];  // records per class (cnt[0] = n)
+  uint64_t any;            // OR of every latency: the bytes above its top bit are zero
+  int32_t top_byte;        // most significant byte with a set bit; -1: every latency is 0
+  rs::State<uint64_t> sel;
 };
-
-typedef uint32_t rec4 __attribute__((ext_vector_type(4)));  // an isim_trace_rec: latency lo, hi, hops, status_err
 
 struct QArgs {
   uint32_t ppm[kMaxQ];
 };
 
 constexpr uint64_t kStateBytes = (sizeof(QState) + 255) & ~255ull;
+static_assert(kStateBytes == 1536, "isim_quantiles_workspace_bytes is pinned");
 
 uint64_t workspace_bytes(uint32_t n_q) { return kStateBytes + (uint64_t)kClasses * n_q * kBins * 8; }
 
@@ -75,10 +65,9 @@ __global__ __launch_bounds__(256) void k_quantile_count(const rec4 *__restrict__
   unsigned long long any = 0, n500 = 0;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    rec4 r = rec[i];
-    asm volatile("" : "+v"(r));  // all four words stay live: the record is one 16-byte load (hops is unused)
-    any |= (unsigned long long)r.x | ((unsigned long long)r.y << 32);
-    n500 += r.w >> 31;
+    const rec4 r = isim::dev::load_rec(rec, i);
+    any |= isim::dev::latency(r);
+    n500 += isim::dev::code(r);
   }
   for (int d = 32; d; d >>= 1) {
     any |= __shfl_xor(any, d, 64);
@@ -108,39 +97,13 @@ __global__ __launch_bounds__(64) void k_quantile_setup(QState *st, uint64_t n, Q
   const uint64_t cnt[kClasses] = {n, n - n500, n500};
   if (t < kClasses * kMaxQ) {
     const uint32_t c = t / kMaxQ, i = t % kMaxQ;
-    if (i < n_q) {
-      st->prefix[c][i] = 0;
-      st->k[c][i] = cnt[c] ? nearest_rank(cnt[c], q.ppm[i]) : 0;
-      st->grp[c][i] = 0;
-    }
+    rs::init(st->sel, c, i, n_q, cnt[c], q.ppm);
     if (i == 0) {
       st->cnt[c] = cnt[c];
-      st->ngrp[c] = cnt[c] ? 1u : 0u;
-      st->gprefix[c][0] = 0;
       out[c * (1 + n_q)] = cnt[c];
     }
   }
-  if (t == 0) st->top_byte = any ? (63 - __clzll((long long)any)) >> 3 : -1;
-}
-
-// One LDS bin per lane (bin < 0: none).  Lanes of a wave that hit the same bin
-// add once: the first pending lane's bin is broadcast, the lanes that match it
-// are counted by a ballot and their leader adds the count.  A constant batch
-// (a static walk without draws) takes one round; a wave whose bins are spread
-// leaves the peel at the first bin shared by fewer than four lanes and the
-// rest add one each.
-__device__ __forceinline__ void wave_add(uint32_t *hist, int bin) {
-  unsigned long long rem = __ballot(bin >= 0);
-  while (rem) {
-    const int lead = __ffsll((long long)rem) - 1;
-    const int b0 = __builtin_amdgcn_readlane(bin, lead);
-    const unsigned long long m = __ballot(bin == b0);
-    if (__popcll(m) < 4) break;
-    if ((int)(threadIdx.x & 63u) == lead) atomicAdd(&hist[b0], (uint32_t)__popcll(m));
-    if (bin == b0) bin = -1;
-    rem &= ~m;
-  }
-  if (rem && bin >= 0) atomicAdd(&hist[bin], 1u);
+  if (t == 0) st->top_byte = rs::top_byte(any);
 }
 
 // Digit pass `byte`: per (class, group) a 256-bin histogram of that byte over
@@ -155,8 +118,8 @@ __global__ __launch_bounds__(kHistThreads) void k_quantile_hist(const rec4 *__re
   __shared__ uint32_t s_ngrp[kClasses];
   if (byte > st->top_byte) return;  // every latency is zero in this byte: the prefixes keep a zero digit
   const uint32_t t = threadIdx.x;
-  if (t < kClasses) s_ngrp[t] = min(st->ngrp[t], n_q);
-  if (t < kClasses * kMaxQ) s_prefix[t / kMaxQ][t % kMaxQ] = st->gprefix[t / kMaxQ][t % kMaxQ];
+  if (t < kClasses) s_ngrp[t] = min(st->sel.ngrp[t], n_q);
+  if (t < kClasses * kMaxQ) s_prefix[t / kMaxQ][t % kMaxQ] = st->sel.gprefix[t / kMaxQ][t % kMaxQ];
   __syncthreads();
   uint32_t ngrp[kClasses];
   for (uint32_t c = 0; c < kClasses; ++c) {
@@ -165,9 +128,7 @@ __global__ __launch_bounds__(kHistThreads) void k_quantile_hist(const rec4 *__re
   }
   __syncthreads();
 
-  const uint32_t shift = 8u * (uint32_t)byte;
   const uint32_t lane = t & 63u;
-  const uint32_t ng_max = max(ngrp[ISIM_Q_200], ngrp[ISIM_Q_500]);
   const uint64_t wave = (uint64_t)blockIdx.x * (kHistThreads / 64) + (t >> 6);
   const uint64_t step = (uint64_t)gridDim.x * (kHistThreads / 64) * (64 * kUnroll);
   // a wave takes 64 * kUnroll consecutive records per step; the loop bound is wave-uniform
@@ -176,25 +137,12 @@ __global__ __launch_bounds__(kHistThreads) void k_quantile_hist(const rec4 *__re
 #pragma unroll
     for (uint32_t u = 0; u < kUnroll; ++u) {
       const uint64_t i = base + u * 64 + lane;
-      r[u] = i < n ? rec[i] : rec4{0, 0, 0, 0};
-      asm volatile("" : "+v"(r[u]));  // all four words stay live: the record is one 16-byte load (hops is unused)
+      r[u] = isim::dev::load_rec(rec, i, i < n);
     }
 #pragma unroll
-    for (uint32_t u = 0; u < kUnroll; ++u) {
-      const bool live = base + u * 64 + lane < n;
-      const uint64_t key = (uint64_t)r[u].x | ((uint64_t)r[u].y << 32);
-      const uint32_t digit = (uint32_t)(key >> shift) & 255u;
-      const uint64_t hi = byte == 7 ? 0 : key >> (shift + 8);
-      const uint32_t cls = 1u + (r[u].w >> 31);
-      int bin_all = -1, bin_cls = -1;
-      for (uint32_t g = 0; g < ngrp[0]; ++g)
-        if (s_prefix[0][g] == hi) bin_all = (int)(g * kBins + digit);
-      const uint32_t ng = cls == ISIM_Q_200 ? ngrp[ISIM_Q_200] : ngrp[ISIM_Q_500];
-      for (uint32_t g = 0; g < ng_max; ++g)  // a wave-uniform trip count
-        if (g < ng && s_prefix[cls][g] == hi) bin_cls = (int)((cls * kMaxQ + g) * kBins + digit);
-      wave_add(hist, live ? bin_all : -1);
-      wave_add(hist, live ? bin_cls : -1);
-    }
+    for (uint32_t u = 0; u < kUnroll; ++u)
+      rs::count_key(hist, isim::dev::latency(r[u]), base + u * 64 + lane < n, byte, 1u + isim::dev::code(r[u]), s_prefix,
+                    ngrp[ISIM_Q_ALL], ngrp[ISIM_Q_200], ngrp[ISIM_Q_500], lane);
   }
   __syncthreads();
   for (uint32_t c = 0; c < kClasses; ++c)
@@ -204,70 +152,33 @@ __global__ __launch_bounds__(kHistThreads) void k_quantile_hist(const rec4 *__re
     }
 }
 
-// After digit pass `byte`: per (class, quantile) the digit at which the
-// running count of its group's bins reaches k; the digit joins the prefix and
-// the bins below it leave k.  Then the distinct prefixes of each class become
-// the next pass's groups and the histogram is cleared.  One workgroup, wave i
-// takes quantile i of every class.  After byte 0 the prefixes are the values.
+// After digit pass `byte`: the resolve per (class, quantile), then the regroup
+// (radix_select.h), and the histogram is cleared.  One workgroup, wave i takes
+// quantile i of every class.  After byte 0 the prefixes are the values.
 __global__ __launch_bounds__(kResolveThreads) void k_quantile_resolve(QState *st, unsigned long long *ghist,
                                                                      uint32_t n_q, int byte, uint64_t *out) {
   const uint32_t t = threadIdx.x, lane = t & 63u, i = t >> 6;
   if (byte <= st->top_byte) {
     if (i < n_q) {
       for (uint32_t c = 0; c < kClasses; ++c) {
-        const uint64_t k = st->k[c][i];
+        const uint64_t k = st->sel.k[c][i];
         if (!k) continue;  // empty class
-        const uint32_t g = min(st->grp[c][i], n_q - 1);
+        const uint32_t g = min(st->sel.grp[c][i], n_q - 1);
         const unsigned long long *h = ghist + ((uint64_t)c * n_q + g) * kBins + lane * 4;
-        const uint64_t b0 = h[0], b1 = h[1], b2 = h[2], b3 = h[3];
-        uint64_t incl = b0 + b1 + b2 + b3;
-        for (int d = 1; d < 64; d <<= 1) {
-          const uint64_t up = __shfl_up((unsigned long long)incl, d, 64);
-          if ((int)lane >= d) incl += up;
-        }
-        const uint64_t excl = incl - (b0 + b1 + b2 + b3);
-        // the first lane whose running count reaches k holds the digit; if the records changed under
-        // the select and none does, the last lane takes it, so the digit stays a byte
-        const unsigned long long reach = __ballot(incl >= k);
-        const uint32_t owner = reach ? (uint32_t)__ffsll((long long)reach) - 1u : 63u;
-        if (lane == owner) {
-          uint64_t below = excl;
-          uint32_t d = 0;
-          if (below + b0 < k) {
-            below += b0;
-            d = 1;
-            if (below + b1 < k) {
-              below += b1;
-              d = 2;
-              if (below + b2 < k) {
-                below += b2;
-                d = 3;
-              }
-            }
-          }
-          st->prefix[c][i] = (st->prefix[c][i] << 8) | (lane * 4 + d);
-          st->k[c][i] = k - below;
-        }
+        uint32_t digit;
+        uint64_t below;
+        if (rs::resolve<uint64_t>(h[0], h[1], h[2], h[3], k, lane, digit, below))
+          rs::take_digit(st->sel, c, i, digit, k, below);
       }
     }
     __syncthreads();  // every wave has read its bins and written its prefix
-    if (t < kClasses && st->ngrp[t]) {
-      uint32_t ng = 0;
-      for (uint32_t q = 0; q < n_q; ++q) {
-        const uint64_t p = st->prefix[t][q];
-        uint32_t g = 0;
-        while (g < ng && st->gprefix[t][g] != p) ++g;
-        if (g == ng) st->gprefix[t][ng++] = p;
-        st->grp[t][q] = g;
-      }
-      st->ngrp[t] = ng;
-    }
+    if (t < kClasses) rs::regroup(st->sel, t, n_q);
     for (uint32_t w = t; w < kClasses * n_q * kBins; w += kResolveThreads) ghist[w] = 0;
   }
   if (byte == 0) {
     __syncthreads();
     if (t < kClasses * kMaxQ && t % kMaxQ < n_q)
-      out[(t / kMaxQ) * (1 + n_q) + 1 + t % kMaxQ] = st->k[t / kMaxQ][t % kMaxQ] ? st->prefix[t / kMaxQ][t % kMaxQ] : 0;
+      out[(t / kMaxQ) * (1 + n_q) + 1 + t % kMaxQ] = st->sel.k[t / kMaxQ][t % kMaxQ] ? st->sel.prefix[t / kMaxQ][t % kMaxQ] : 0;
   }
 }
 
@@ -311,7 +222,7 @@ int isim_latency_quantiles_device(const isim_trace_rec *d_records, uint64_t n_re
   if (n_records == 0) {
     hipLaunchKernelGGL(k_quantile_clear, dim3(1), dim3(1024), 0, s, (unsigned long long *)d_out,
                        (uint32_t)ISIM_Q_OUT_WORDS(n_q));
-    QHIPCHK(hipGetLastError());
+    ISIM_HIPCHK(hipGetLastError());
     return ISIM_OK;
   }
   QState *st = (QState *)d_workspace;
@@ -331,7 +242,7 @@ int isim_latency_quantiles_device(const isim_trace_rec *d_records, uint64_t n_re
                        (const QState *)st, ghist, n_q, byte);
     hipLaunchKernelGGL(k_quantile_resolve, dim3(1), dim3(kResolveThreads), 0, s, st, ghist, n_q, byte, d_out);
   }
-  QHIPCHK(hipGetLastError());
+  ISIM_HIPCHK(hipGetLastError());
   return ISIM_OK;
 }
 
@@ -339,41 +250,15 @@ int isim_latency_quantiles(int device, const isim_trace_rec *h_records, uint64_t
                            uint32_t n_q, uint64_t *h_out) {
   if (const int rc = check_q(q_ppm, n_q, n_records)) return rc;
   if (!h_out || (n_records && !h_records)) return qfail("null argument");
-  int prev = 0;
-  QHIPCHK(hipGetDevice(&prev));
-  QHIPCHK(hipSetDevice(device));
   const uint64_t wsb = workspace_bytes(n_q), out_bytes = ISIM_Q_OUT_WORDS(n_q) * 8;
-  void *d_rec = nullptr, *d_ws = nullptr, *d_out = nullptr;
-  hipStream_t s = nullptr;
-  int rc = ISIM_OK;
-  do {
-    if (hipStreamCreate(&s) != hipSuccess || hipMalloc(&d_ws, wsb) != hipSuccess ||
-        hipMalloc(&d_out, out_bytes) != hipSuccess ||
-        (n_records && hipMalloc(&d_rec, n_records * sizeof(isim_trace_rec)) != hipSuccess)) {
-      rc = isim::set_error(ISIM_EHIP, "quantile buffers: hipMalloc failed");
-      break;
-    }
-    if (n_records && hipMemcpyAsync(d_rec, h_records, n_records * sizeof(isim_trace_rec), hipMemcpyHostToDevice,
-                                    s) != hipSuccess) {
-      rc = isim::set_error(ISIM_EHIP, "copy records failed");
-      break;
-    }
-    rc = isim_latency_quantiles_device((const isim_trace_rec *)d_rec, n_records, q_ppm, n_q, (uint64_t *)d_out, d_ws,
-                                       wsb, s);
-    if (rc != ISIM_OK) break;
-    if (const hipError_t e = hipStreamSynchronize(s); e != hipSuccess) {
-      rc = isim::set_error(ISIM_EHIP, std::string("quantile kernels failed: ") + hipGetErrorString(e));
-      break;
-    }
-    if (hipMemcpy(h_out, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = isim::set_error(ISIM_EHIP, "copy quantiles failed");
-  } while (0);
-  if (d_rec) (void)hipFree(d_rec);
-  if (d_ws) (void)hipFree(d_ws);
-  if (d_out) (void)hipFree(d_out);
-  if (s) (void)hipStreamDestroy(s);
-  (void)hipSetDevice(prev);
-  return rc;
+  isim::HostStage stage(device);
+  void *d_ws = stage.alloc(wsb), *d_out = stage.alloc(out_bytes);
+  void *d_rec = stage.upload(h_records, n_records * sizeof(isim_trace_rec));
+  if (stage.rc() != ISIM_OK) return stage.rc();
+  if (const int rc = isim_latency_quantiles_device((const isim_trace_rec *)d_rec, n_records, q_ppm, n_q,
+                                                   (uint64_t *)d_out, d_ws, wsb, stage.stream()))
+    return rc;
+  return stage.download(h_out, d_out, out_bytes);
 }
 
 }  // extern "C"

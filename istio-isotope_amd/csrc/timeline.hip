@@ -23,13 +23,14 @@
 
 #include "../../include/isim.h"
 #include "des_bucket.h"
+#include "host_stage.h"
 #include "timeline_row.h"
-
-namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-}
+#include "trace_rec_dev.h"
+#include "wave_peel.h"
 
 namespace {
+
+using isim::dev::rec4;
 
 constexpr uint32_t kW = ISIM_TL_ROW_WORDS;
 constexpr uint32_t kThreads = 256;
@@ -45,14 +46,6 @@ static_assert(kW == 7 + 2 * ISIM_N_PROM, "row layout");
 static_assert((uint64_t)(ISIM_TL_MAX_WINDOWS + 2) * kW < (1ull << 31), "word indices fit 32 bits");
 
 int tfail(const std::string &msg) { return isim::set_error(ISIM_EINVAL, msg); }
-
-#define THIPCHK(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return isim::set_error(ISIM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-typedef uint32_t rec4 __attribute__((ext_vector_type(4)));  // an isim_trace_rec: latency lo, hi, hops, status_err
 
 struct TlArgs {
   const uint64_t *arr;
@@ -116,53 +109,41 @@ __device__ __forceinline__ void tl_max(const Tile &t, uint32_t row, uint32_t off
   else atomicMax(&t.out[(uint64_t)row * kW + off], (unsigned long long)v);
 }
 
-// word[key] += 1 per lane (key = row * kW + offset; kNone: no update).  The
-// first pending lane's key is broadcast, the lanes that match are counted by a
-// ballot and their leader adds the count; after kPeel shared keys, or at the
-// first key shared by fewer than four lanes, the rest add one each.
+// word[key] += 1 per lane (key = row * kW + offset; kNone: no update): the
+// peel of wave_peel.h, at most kPeel shared keys before the rest add one each
 __device__ __forceinline__ void wave_count(const Tile &t, uint32_t key) {
-  unsigned long long rem = __ballot(key != kNone);
-  for (uint32_t it = 0; it < kPeel && rem; ++it) {
-    const int lead = __ffsll((long long)rem) - 1;
-    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
-    const unsigned long long m = __ballot(key == k0);
-    if (__popcll(m) < 4) break;
-    if ((int)(threadIdx.x & 63u) == lead) tl_add(t, k0 / kW, k0 % kW, (uint64_t)__popcll(m));
-    if (key == k0) key = kNone;
-    rem &= ~m;
-  }
-  if (key != kNone) tl_add(t, key / kW, key % kW, 1);
+  isim::dev::wave_peel<kPeel>(
+      key, kNone,
+      [&](uint32_t k0, unsigned long long m, int lead) {
+        if ((int)(threadIdx.x & 63u) == lead) tl_add(t, k0 / kW, k0 % kW, (uint64_t)__popcll(m));
+      },
+      [&](uint32_t k) { tl_add(t, k / kW, k % kW, 1); });
 }
 
 // the completion words of (row, code) = key >> 1, key & 1: count, latency sum
 // and latency maximum, added up the same way
 __device__ __forceinline__ void wave_done(const Tile &t, uint32_t key, uint64_t lat) {
-  unsigned long long rem = __ballot(key != kNone);
-  for (uint32_t it = 0; it < kPeel && rem; ++it) {
-    const int lead = __ffsll((long long)rem) - 1;
-    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
-    const bool mine = key == k0;
-    const unsigned long long m = __ballot(mine);
-    if (__popcll(m) < 4) break;
-    const uint64_t sum = wave_reduce<OpAdd>(mine ? lat : 0);
-    const uint64_t mx = wave_reduce<OpMax>(mine ? lat : 0);
-    if ((int)(threadIdx.x & 63u) == lead) {
-      const uint32_t row = k0 >> 1, code = k0 & 1u;
-      tl_add(t, row, ISIM_TL_DONE + code, (uint64_t)__popcll(m));
-      if (sum) tl_add(t, row, ISIM_TL_SUM_LAT + code, sum);
-      if (mx) tl_max(t, row, ISIM_TL_MAX_LAT + code, mx);
-    }
-    if (mine) key = kNone;
-    rem &= ~m;
-  }
-  if (key != kNone) {
-    const uint32_t row = key >> 1, code = key & 1u;
-    tl_add(t, row, ISIM_TL_DONE + code, 1);
-    if (lat) {
-      tl_add(t, row, ISIM_TL_SUM_LAT + code, lat);
-      tl_max(t, row, ISIM_TL_MAX_LAT + code, lat);
-    }
-  }
+  isim::dev::wave_peel<kPeel>(
+      key, kNone,
+      [&](uint32_t k0, unsigned long long m, int lead) {
+        const bool mine = key == k0;
+        const uint64_t sum = wave_reduce<OpAdd>(mine ? lat : 0);
+        const uint64_t mx = wave_reduce<OpMax>(mine ? lat : 0);
+        if ((int)(threadIdx.x & 63u) == lead) {
+          const uint32_t row = k0 >> 1, code = k0 & 1u;
+          tl_add(t, row, ISIM_TL_DONE + code, (uint64_t)__popcll(m));
+          if (sum) tl_add(t, row, ISIM_TL_SUM_LAT + code, sum);
+          if (mx) tl_max(t, row, ISIM_TL_MAX_LAT + code, mx);
+        }
+      },
+      [&](uint32_t k) {
+        const uint32_t row = k >> 1, code = k & 1u;
+        tl_add(t, row, ISIM_TL_DONE + code, 1);
+        if (lat) {
+          tl_add(t, row, ISIM_TL_SUM_LAT + code, lat);
+          tl_max(t, row, ISIM_TL_MAX_LAT + code, lat);
+        }
+      });
 }
 
 __global__ __launch_bounds__(kThreads) void k_timeline(TlArgs a) {
@@ -187,9 +168,8 @@ __global__ __launch_bounds__(kThreads) void k_timeline(TlArgs a) {
     for (uint32_t u = 0; u < kUnroll; ++u) {
       const uint64_t i = base + u * 64 + lane;
       const bool live = i < a.n;
-      r[u] = live ? a.rec[i] : rec4{0, 0, 0, 0};
       arr[u] = live ? a.arr[i] : 0;
-      asm volatile("" : "+v"(r[u]));  // all four words stay live: the record is one 16-byte load (hops is unused)
+      r[u] = isim::dev::load_rec(a.rec, i, live);
     }
     uint32_t ra[kUnroll], kc[kUnroll], kp[kUnroll];
     uint64_t lat[kUnroll];
@@ -197,10 +177,9 @@ __global__ __launch_bounds__(kThreads) void k_timeline(TlArgs a) {
 #pragma unroll
     for (uint32_t u = 0; u < kUnroll; ++u) {
       const bool live = base + u * 64 + lane < a.n;
-      lat[u] = (uint64_t)r[u].x | ((uint64_t)r[u].y << 32);
-      uint64_t c = arr[u] + lat[u];
-      c = c < arr[u] ? ~0ull : c;  // saturates
-      const uint32_t code = r[u].w >> 31;
+      lat[u] = isim::dev::latency(r[u]);
+      const uint64_t c = isim::dev::completion(arr[u], lat[u]);
+      const uint32_t code = isim::dev::code(r[u]);
       const uint32_t row_a = tl_row(a, arr[u]), row_c = tl_row(a, c);
       ra[u] = live ? row_a * kW + ISIM_TL_ARRIVED : kNone;
       kc[u] = live ? row_c * 2u + code : kNone;
@@ -261,7 +240,7 @@ int isim_timeline_device(const uint64_t *d_arrivals, const isim_trace_rec *d_rec
   isim::tl::set_row_args(a, *p);
   const uint64_t grid = (n + kTile - 1) / kTile;  // n <= 2^40: at most 2^28 workgroups
   hipLaunchKernelGGL(k_timeline, dim3((uint32_t)grid), dim3(kThreads), 0, (hipStream_t)hip_stream, a);
-  THIPCHK(hipGetLastError());
+  ISIM_HIPCHK(hipGetLastError());
   return ISIM_OK;
 }
 
@@ -271,41 +250,15 @@ int isim_timeline(int device, const uint64_t *h_arrivals, const isim_trace_rec *
   if (!h_out) return tfail("null h_out");
   if (n && (!h_arrivals || !h_records)) return tfail("null h_arrivals or h_records");
   if (n == 0) return ISIM_OK;
-  int prev = 0;
-  THIPCHK(hipGetDevice(&prev));
-  THIPCHK(hipSetDevice(device));
   const uint64_t out_bytes = out_words(p->n_windows) * 8;
-  void *d_arr = nullptr, *d_rec = nullptr, *d_out = nullptr;
-  hipStream_t s = nullptr;
-  int rc = ISIM_OK;
-  do {
-    if (hipStreamCreate(&s) != hipSuccess || hipMalloc(&d_out, out_bytes) != hipSuccess ||
-        hipMalloc(&d_arr, n * 8) != hipSuccess || hipMalloc(&d_rec, n * sizeof(isim_trace_rec)) != hipSuccess) {
-      rc = isim::set_error(ISIM_EHIP, "timeline buffers: hipMalloc failed");
-      break;
-    }
-    // h_out is accumulated into like d_out: it goes up first
-    if (hipMemcpyAsync(d_out, h_out, out_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_arr, h_arrivals, n * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_rec, h_records, n * sizeof(isim_trace_rec), hipMemcpyHostToDevice, s) != hipSuccess) {
-      rc = isim::set_error(ISIM_EHIP, "copy timeline inputs failed");
-      break;
-    }
-    rc = isim_timeline_device((const uint64_t *)d_arr, (const isim_trace_rec *)d_rec, n, p, (uint64_t *)d_out, s);
-    if (rc != ISIM_OK) break;
-    if (const hipError_t e = hipStreamSynchronize(s); e != hipSuccess) {
-      rc = isim::set_error(ISIM_EHIP, std::string("timeline kernel failed: ") + hipGetErrorString(e));
-      break;
-    }
-    if (hipMemcpy(h_out, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = isim::set_error(ISIM_EHIP, "copy timeline failed");
-  } while (0);
-  if (d_arr) (void)hipFree(d_arr);
-  if (d_rec) (void)hipFree(d_rec);
-  if (d_out) (void)hipFree(d_out);
-  if (s) (void)hipStreamDestroy(s);
-  (void)hipSetDevice(prev);
-  return rc;
+  isim::HostStage stage(device);
+  void *d_out = stage.upload(h_out, out_bytes);  // h_out is accumulated into like d_out: it goes up first
+  void *d_arr = stage.upload(h_arrivals, n * 8), *d_rec = stage.upload(h_records, n * sizeof(isim_trace_rec));
+  if (stage.rc() != ISIM_OK) return stage.rc();
+  if (const int rc = isim_timeline_device((const uint64_t *)d_arr, (const isim_trace_rec *)d_rec, n, p,
+                                          (uint64_t *)d_out, stage.stream()))
+    return rc;
+  return stage.download(h_out, d_out, out_bytes);
 }
 
 int isim_timeline_merge(uint32_t n_windows, uint64_t *dst, const uint64_t *src) {

@@ -13,18 +13,21 @@
 #include <string>
 
 #include "../../include/isim.h"
+#include "host_stage.h"
 #include "quantile_rank.h"
+#include "radix_select.h"
 #include "timeline_row.h"
-
-namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-}
+#include "trace_rec_dev.h"
+#include "wave_peel.h"
 
 namespace {
 
-constexpr uint32_t kMaxQ = ISIM_MAX_QUANTILES;
-constexpr uint32_t kClasses = 3;
-constexpr uint32_t kBins = 256;
+namespace rs = isim::rs;
+using isim::dev::rec4;
+using rs::kBins;
+using rs::kClasses;
+using rs::kMaxQ;
+
 constexpr uint32_t kThreads = 256;        // count, scatter, clear
 constexpr uint32_t kUnroll = 4;           // records per lane in flight
 constexpr uint32_t kMaxGrid = 2048;       // count and scatter stride past it
@@ -40,13 +43,6 @@ constexpr uint64_t kHeadBytes = 256;      // the row ticket
 
 int tfail(const std::string &msg) { return isim::set_error(ISIM_EINVAL, msg); }
 
-#define TQHIPCHK(expr)                                                                             \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return isim::set_error(ISIM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-typedef uint32_t rec4 __attribute__((ext_vector_type(4)));  // an isim_trace_rec: latency lo, hi, hops, status_err
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // The workspace: the ticket, then three u32 arrays of one word per (row, code)
@@ -95,57 +91,30 @@ __device__ __forceinline__ void load_keys(const TqArgs &a, uint64_t base, uint32
   for (uint32_t u = 0; u < kUnroll; ++u) {
     const uint64_t i = base + u * 64 + lane;
     const bool live = i < a.n;
-    r[u] = live ? a.rec[i] : rec4{0, 0, 0, 0};
     arr[u] = live ? a.arr[i] : 0;
-    asm volatile("" : "+v"(r[u]));  // all four words stay live: the record is one 16-byte load (hops is unused)
+    r[u] = isim::dev::load_rec(a.rec, i, live);
   }
 #pragma unroll
   for (uint32_t u = 0; u < kUnroll; ++u) {
-    lat[u] = (uint64_t)r[u].x | ((uint64_t)r[u].y << 32);
-    uint64_t c = arr[u] + lat[u];
-    c = c < arr[u] ? ~0ull : c;  // saturates
-    key[u] = base + u * 64 + lane < a.n ? isim::tl::row_of(a, c) * 2u + (r[u].w >> 31) : kNone;
+    lat[u] = isim::dev::latency(r[u]);
+    const uint64_t c = isim::dev::completion(arr[u], lat[u]);
+    key[u] = base + u * 64 + lane < a.n ? isim::tl::row_of(a, c) * 2u + isim::dev::code(r[u]) : kNone;
   }
 }
 
-// cnt[key] += 1 per lane (kNone: none).  The first pending lane's key is
-// broadcast, the lanes that match are counted by a ballot and their leader
-// adds the count; at the first key shared by fewer than four lanes the rest
-// add one each.
-__device__ __forceinline__ void wave_count(uint32_t *cnt, uint32_t key, uint32_t lane) {
-  unsigned long long rem = __ballot(key != kNone);
-  while (rem) {
-    const int lead = __ffsll((long long)rem) - 1;
-    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
-    const unsigned long long m = __ballot(key == k0);
-    if (__popcll(m) < 4) break;
-    if ((int)lane == lead) atomicAdd(&cnt[k0], (uint32_t)__popcll(m));
-    if (key == k0) key = kNone;
-    rem &= ~m;
-  }
-  if (key != kNone) atomicAdd(&cnt[key], 1u);
-}
-
-// The same peel for the cursors: the leader claims a run of positions for the
-// lanes that share its key and each takes the one of its rank among them.
+// The peel of the counts (rs::wave_add) for the cursors: the leader claims a run of positions
+// for the lanes that share its key and each takes the one of its rank among them.
 __device__ __forceinline__ uint32_t wave_claim(uint32_t *cur, uint32_t key, uint32_t lane) {
   uint32_t pos = 0;
-  unsigned long long rem = __ballot(key != kNone);
-  while (rem) {
-    const int lead = __ffsll((long long)rem) - 1;
-    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
-    const unsigned long long m = __ballot(key == k0);
-    if (__popcll(m) < 4) break;
-    uint32_t first = 0;
-    if ((int)lane == lead) first = atomicAdd(&cur[k0], (uint32_t)__popcll(m));
-    first = (uint32_t)__builtin_amdgcn_readlane((int)first, lead);
-    if (key == k0) {
-      pos = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      key = kNone;
-    }
-    rem &= ~m;
-  }
-  if (key != kNone) pos = atomicAdd(&cur[key], 1u);
+  isim::dev::wave_peel<isim::dev::kPeelAll>(
+      key, kNone,
+      [&](uint32_t k0, unsigned long long m, int lead) {
+        uint32_t first = 0;
+        if ((int)lane == lead) first = atomicAdd(&cur[k0], (uint32_t)__popcll(m));
+        first = (uint32_t)__builtin_amdgcn_readlane((int)first, lead);
+        if (key == k0) pos = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      },
+      [&](uint32_t k) { pos = atomicAdd(&cur[k], 1u); });
   return pos;
 }
 
@@ -160,7 +129,7 @@ __global__ __launch_bounds__(kThreads) void k_tlq_count(TqArgs a) {
     uint64_t lat[kUnroll];
     load_keys(a, base, lane, key, lat);
 #pragma unroll
-    for (uint32_t u = 0; u < kUnroll; ++u) wave_count(a.cnt, key[u], lane);
+    for (uint32_t u = 0; u < kUnroll; ++u) rs::wave_add(a.cnt, (int)key[u], lane);  // kNone: no bin
   }
 }
 
@@ -229,22 +198,6 @@ __global__ __launch_bounds__(kThreads) void k_tlq_scatter(TqArgs a) {
   }
 }
 
-// quantile.hip's wave_add: one LDS bin per lane (bin < 0: none); lanes of a
-// wave that hit the same bin add once.  A row of equal latencies takes one round.
-__device__ __forceinline__ void wave_add(uint32_t *hist, int bin, uint32_t lane) {
-  unsigned long long rem = __ballot(bin >= 0);
-  while (rem) {
-    const int lead = __ffsll((long long)rem) - 1;
-    const int b0 = __builtin_amdgcn_readlane(bin, lead);
-    const unsigned long long m = __ballot(bin == b0);
-    if (__popcll(m) < 4) break;
-    if ((int)lane == lead) atomicAdd(&hist[b0], (uint32_t)__popcll(m));
-    if (bin == b0) bin = -1;
-    rem &= ~m;
-  }
-  if (rem && bin >= 0) atomicAdd(&hist[bin], 1u);
-}
-
 struct SelArgs {
   const uint32_t *cnt;             // [rows][2]
   const uint32_t *off;             // [rows][2]
@@ -255,14 +208,11 @@ struct SelArgs {
   uint32_t ppm[kMaxQ];
 };
 
+// The select's state of a workgroup's row (radix_select.h); the row's ticket is sel.owner_word,
+// which keeps the struct, and with it the kernel's LDS, at its size.
 struct SelState {
-  unsigned long long prefix[kClasses][kMaxQ];   // per quantile: the digits chosen so far
-  unsigned long long gprefix[kClasses][kMaxQ];  // per group: the digits chosen so far
-  unsigned long long any[kSelWaves];            // per wave: OR of the row's latencies
-  uint32_t k[kClasses][kMaxQ];                  // per quantile: 1-based rank among the latencies under its prefix
-  uint32_t grp[kClasses][kMaxQ];                // per quantile: its group
-  uint32_t ngrp[kClasses];                      // groups per class (0: the class is empty)
-  uint32_t row;
+  rs::State<uint32_t> sel;
+  unsigned long long any[kSelWaves];  // per wave: OR of the row's latencies
 };
 
 // One digit of a row: per (class, group) the 256-bin histogram of byte `byte`
@@ -273,8 +223,6 @@ __device__ __forceinline__ void digit_pass(uint32_t *hist, const SelState &s, co
                                            const unsigned long long *seg, uint32_t n_row, uint32_t n200, int byte,
                                            uint32_t ng_all, uint32_t ng_200, uint32_t ng_500, uint32_t lane,
                                            uint32_t wave) {
-  const uint32_t shift = 8u * (uint32_t)byte;
-  const uint32_t ng_max = max(ng_200, ng_500);
   // a wave takes 64 * kUnroll consecutive latencies per step; the loop bound is wave-uniform
   for (uint64_t base = (uint64_t)wave * (64 * kUnroll); base < n_row; base += (uint64_t)kSelWaves * (64 * kUnroll)) {
     unsigned long long key[kUnroll];
@@ -286,18 +234,8 @@ __device__ __forceinline__ void digit_pass(uint32_t *hist, const SelState &s, co
 #pragma unroll
     for (uint32_t u = 0; u < kUnroll; ++u) {
       const uint64_t i = base + u * 64 + lane;
-      const bool live = i < n_row;
-      const uint32_t digit = (uint32_t)(key[u] >> shift) & 255u;
-      const unsigned long long hi = byte == 7 ? 0 : key[u] >> (shift + 8);
-      const uint32_t cls = i < n200 ? ISIM_Q_200 : ISIM_Q_500;
-      int bin_all = -1, bin_cls = -1;
-      for (uint32_t g = 0; g < ng_all; ++g)
-        if (s.gprefix[0][g] == hi) bin_all = (int)(g * kBins + digit);
-      const uint32_t ng = cls == ISIM_Q_200 ? ng_200 : ng_500;
-      for (uint32_t g = 0; g < ng_max; ++g)  // a wave-uniform trip count
-        if (g < ng && s.gprefix[cls][g] == hi) bin_cls = (int)((cls * kMaxQ + g) * kBins + digit);
-      wave_add(hist, live ? bin_all : -1, lane);
-      wave_add(hist, live ? bin_cls : -1, lane);
+      rs::count_key(hist, key[u], i < n_row, byte, i < n200 ? ISIM_Q_200 : ISIM_Q_500, s.sel.gprefix, ng_all, ng_200,
+                    ng_500, lane);
     }
   }
 }
@@ -305,9 +243,8 @@ __device__ __forceinline__ void digit_pass(uint32_t *hist, const SelState &s, co
 // The select.  A workgroup claims rows through the ticket until none is left.
 // An empty row gets its zeros; otherwise the row's OR gives the top byte and
 // from there down each digit is a histogram pass, a resolve (a wave per
-// (class, quantile): the digit at which the running count of its group's bins
-// reaches k joins the prefix, the bins below leave k) and a regrouping of the
-// distinct prefixes.  After byte 0 the prefixes are the values.
+// (class, quantile)) and a regroup (radix_select.h).  After byte 0 the
+// prefixes are the values.
 __global__ __launch_bounds__(kSelThreads) void k_tlq_select(SelArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t hist[kClasses * kMaxQ * kBins];
   __shared__ unsigned long long s_stage[kStage];
@@ -316,9 +253,9 @@ __global__ __launch_bounds__(kSelThreads) void k_tlq_select(SelArgs a) {
   const uint32_t n_q = a.n_q, ow = 1u + n_q;
   for (;;) {
     __syncthreads();  // the previous row's state has been read
-    if (t == 0) s.row = atomicAdd(a.ticket, 1u);
+    if (t == 0) s.sel.owner_word = atomicAdd(a.ticket, 1u);
     __syncthreads();
-    const uint32_t row = s.row;
+    const uint32_t row = s.sel.owner_word;
     if (row >= a.rows) return;  // workgroup-uniform
     const uint32_t n200 = a.cnt[2 * row], n500 = a.cnt[2 * row + 1];
     const uint32_t n_row = n200 + n500;  // at most n < 2^32
@@ -345,25 +282,16 @@ __global__ __launch_bounds__(kSelThreads) void k_tlq_select(SelArgs a) {
     if (t < kClasses * kMaxQ) {
       const uint32_t c = t / kMaxQ, i = t % kMaxQ;
       const uint32_t n_c = c == ISIM_Q_ALL ? n_row : c == ISIM_Q_200 ? n200 : n500;
-      if (i < n_q) {
-        s.prefix[c][i] = 0;
-        s.k[c][i] = n_c ? (uint32_t)isim::q::nearest_rank(n_c, a.ppm[i]) : 0u;
-        s.grp[c][i] = 0;
-      }
-      if (i == 0) {
-        s.ngrp[c] = n_c ? 1u : 0u;
-        s.gprefix[c][0] = 0;
-        out[c * ow] = n_c;
-      }
+      rs::init(s.sel, c, i, n_q, n_c, a.ppm);
+      if (i == 0) out[c * ow] = n_c;
     }
     __syncthreads();
     any = 0;
     for (uint32_t w = 0; w < kSelWaves; ++w) any |= s.any[w];
-    const int top_byte = any ? (63 - __clzll((long long)any)) >> 3 : -1;  // the bytes above it are zero: so are their digits
 
-    for (int byte = top_byte; byte >= 0; --byte) {
-      const uint32_t ng_all = min(s.ngrp[ISIM_Q_ALL], n_q), ng_200 = min(s.ngrp[ISIM_Q_200], n_q),
-                     ng_500 = min(s.ngrp[ISIM_Q_500], n_q);
+    for (int byte = rs::top_byte(any); byte >= 0; --byte) {
+      const uint32_t ng_all = min(s.sel.ngrp[ISIM_Q_ALL], n_q), ng_200 = min(s.sel.ngrp[ISIM_Q_200], n_q),
+                     ng_500 = min(s.sel.ngrp[ISIM_Q_500], n_q);
       for (uint32_t i = t; i < ng_all * kBins; i += kSelThreads) hist[i] = 0;
       for (uint32_t i = t; i < ng_200 * kBins; i += kSelThreads) hist[ISIM_Q_200 * kMaxQ * kBins + i] = 0;
       for (uint32_t i = t; i < ng_500 * kBins; i += kSelThreads) hist[ISIM_Q_500 * kMaxQ * kBins + i] = 0;
@@ -373,55 +301,20 @@ __global__ __launch_bounds__(kSelThreads) void k_tlq_select(SelArgs a) {
       __syncthreads();
       for (uint32_t task = wave; task < kClasses * n_q; task += kSelWaves) {  // wave-uniform
         const uint32_t c = task / n_q, i = task % n_q;
-        const uint32_t k = s.k[c][i];
+        const uint32_t k = s.sel.k[c][i];
         if (!k) continue;  // empty class
-        const uint32_t g = min(s.grp[c][i], n_q - 1);
-        const u32x4 b = *reinterpret_cast<const u32x4 *>(hist + (c * kMaxQ + g) * kBins + lane * 4);
-        const uint32_t sum = b.x + b.y + b.z + b.w;  // at most n_row
-        uint32_t incl = sum;
-        for (int d = 1; d < 64; d <<= 1) {
-          const uint32_t up = __shfl_up(incl, d, 64);
-          if ((int)lane >= d) incl += up;
-        }
-        // the first lane whose running count reaches k holds the digit; the last lane takes it if none
-        // does (it cannot happen for bins that count the row), so the digit stays a byte
-        const unsigned long long reach = __ballot(incl >= k);
-        const uint32_t owner = reach ? (uint32_t)__ffsll((long long)reach) - 1u : 63u;
-        if (lane == owner) {
-          uint32_t below = incl - sum, d = 0;
-          if (below + b.x < k) {
-            below += b.x;
-            d = 1;
-            if (below + b.y < k) {
-              below += b.y;
-              d = 2;
-              if (below + b.z < k) {
-                below += b.z;
-                d = 3;
-              }
-            }
-          }
-          s.prefix[c][i] = (s.prefix[c][i] << 8) | (lane * 4 + d);
-          s.k[c][i] = k - below;
-        }
+        const uint32_t g = min(s.sel.grp[c][i], n_q - 1);
+        const u32x4 b = *reinterpret_cast<const u32x4 *>(hist + (c * kMaxQ + g) * kBins + lane * 4);  // they sum to at most n_row
+        uint32_t digit, below;
+        if (rs::resolve<uint32_t>(b.x, b.y, b.z, b.w, k, lane, digit, below)) rs::take_digit(s.sel, c, i, digit, k, below);
       }
       __syncthreads();
-      if (t < kClasses && s.ngrp[t]) {
-        uint32_t ng = 0;
-        for (uint32_t q = 0; q < n_q; ++q) {
-          const unsigned long long p = s.prefix[t][q];
-          uint32_t g = 0;
-          while (g < ng && s.gprefix[t][g] != p) ++g;
-          if (g == ng) s.gprefix[t][ng++] = p;
-          s.grp[t][q] = g;
-        }
-        s.ngrp[t] = ng;
-      }
+      if (t < kClasses) rs::regroup(s.sel, t, n_q);
       __syncthreads();
     }
     if (t < kClasses * kMaxQ && t % kMaxQ < n_q) {
       const uint32_t c = t / kMaxQ, i = t % kMaxQ;
-      out[c * ow + 1 + i] = s.k[c][i] ? s.prefix[c][i] : 0;
+      out[c * ow + 1 + i] = s.sel.k[c][i] ? s.sel.prefix[c][i] : 0;
     }
   }
 }
@@ -470,7 +363,7 @@ int isim_timeline_quantiles_device(const uint64_t *d_arrivals, const isim_trace_
     const uint64_t words = 2 * ISIM_TLQ_OUT_WORDS(p->n_windows, n_q);  // u32
     hipLaunchKernelGGL(k_tlq_clear, dim3(grid_for(words, kThreads * 4, kMaxGrid)), dim3(kThreads), 0, s,
                        (uint32_t *)d_out, words);
-    TQHIPCHK(hipGetLastError());
+    ISIM_HIPCHK(hipGetLastError());
     return ISIM_OK;
   }
   char *ws = (char *)d_workspace;
@@ -502,7 +395,7 @@ int isim_timeline_quantiles_device(const uint64_t *d_arrivals, const isim_trace_
                      a.cur, (uint32_t)l.counters);
   hipLaunchKernelGGL(k_tlq_scatter, dim3(grid), dim3(kThreads), 0, s, a);
   hipLaunchKernelGGL(k_tlq_select, dim3(std::min(rows, kSelMaxGrid)), dim3(kSelThreads), 0, s, sel);
-  TQHIPCHK(hipGetLastError());
+  ISIM_HIPCHK(hipGetLastError());
   return ISIM_OK;
 }
 
@@ -511,42 +404,15 @@ int isim_timeline_quantiles(int device, const uint64_t *h_arrivals, const isim_t
   if (const int rc = check_common(p, q_ppm, n_q, n)) return rc;
   if (!h_out) return tfail("null h_out");
   if (n && (!h_arrivals || !h_records)) return tfail("null h_arrivals or h_records");
-  int prev = 0;
-  TQHIPCHK(hipGetDevice(&prev));
-  TQHIPCHK(hipSetDevice(device));
   const uint64_t out_bytes = ISIM_TLQ_OUT_WORDS(p->n_windows, n_q) * 8, wsb = layout(n, p->n_windows).total;
-  void *d_arr = nullptr, *d_rec = nullptr, *d_out = nullptr, *d_ws = nullptr;
-  hipStream_t s = nullptr;
-  int rc = ISIM_OK;
-  do {
-    if (hipStreamCreate(&s) != hipSuccess || hipMalloc(&d_out, out_bytes) != hipSuccess ||
-        hipMalloc(&d_ws, wsb) != hipSuccess ||
-        (n && (hipMalloc(&d_arr, n * 8) != hipSuccess || hipMalloc(&d_rec, n * sizeof(isim_trace_rec)) != hipSuccess))) {
-      rc = isim::set_error(ISIM_EHIP, "timeline quantile buffers: hipMalloc failed");
-      break;
-    }
-    if (n && (hipMemcpyAsync(d_arr, h_arrivals, n * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-              hipMemcpyAsync(d_rec, h_records, n * sizeof(isim_trace_rec), hipMemcpyHostToDevice, s) != hipSuccess)) {
-      rc = isim::set_error(ISIM_EHIP, "copy timeline quantile inputs failed");
-      break;
-    }
-    rc = isim_timeline_quantiles_device((const uint64_t *)d_arr, (const isim_trace_rec *)d_rec, n, p, q_ppm, n_q,
-                                        (uint64_t *)d_out, d_ws, wsb, s);
-    if (rc != ISIM_OK) break;
-    if (const hipError_t e = hipStreamSynchronize(s); e != hipSuccess) {
-      rc = isim::set_error(ISIM_EHIP, std::string("timeline quantile kernels failed: ") + hipGetErrorString(e));
-      break;
-    }
-    if (hipMemcpy(h_out, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = isim::set_error(ISIM_EHIP, "copy timeline quantiles failed");
-  } while (0);
-  if (d_arr) (void)hipFree(d_arr);
-  if (d_rec) (void)hipFree(d_rec);
-  if (d_out) (void)hipFree(d_out);
-  if (d_ws) (void)hipFree(d_ws);
-  if (s) (void)hipStreamDestroy(s);
-  (void)hipSetDevice(prev);
-  return rc;
+  isim::HostStage stage(device);
+  void *d_out = stage.alloc(out_bytes), *d_ws = stage.alloc(wsb);
+  void *d_arr = stage.upload(h_arrivals, n * 8), *d_rec = stage.upload(h_records, n * sizeof(isim_trace_rec));
+  if (stage.rc() != ISIM_OK) return stage.rc();
+  if (const int rc = isim_timeline_quantiles_device((const uint64_t *)d_arr, (const isim_trace_rec *)d_rec, n, p, q_ppm,
+                                                    n_q, (uint64_t *)d_out, d_ws, wsb, stage.stream()))
+    return rc;
+  return stage.download(h_out, d_out, out_bytes);
 }
 
 }  // extern "C"

@@ -108,6 +108,29 @@ def test_constant_latency(gpu):
     assert (got[native.Q_500, 1:] == v).all() and got[native.Q_200, 0] + got[native.Q_500, 0] == 100_000
 
 
+def peel_lanes():
+    """64 lane slots for one wave: slot values 5, 4, 3 and 1 held by that many lanes, 0 by the other 51.  In
+    lane order the peel (csrc/wave_peel.h) takes the 0s, the 5s and the 4s as shared keys and leaves at the 3s;
+    reversed it takes the 0s and leaves at the 1, so the 3s, 4s and 5s go singly."""
+    lanes = [0] * 7 + [5] * 2 + [4] + [0] * 10 + [5] * 3 + [4] * 3 + [3] * 3 + [1] + [0] * 34
+    assert len(lanes) == 64 and [lanes.count(v) for v in (1, 3, 4, 5, 0)] == [1, 3, 4, 5, 51]
+    return np.array(lanes, U64)
+
+
+def test_peel_threshold(gpu):
+    """One wave whose latencies differ in byte 1 and byte 0 with multiplicities on both sides of the peel's
+    'fewer than four' break, in lane order and reversed (another leader, another break point)."""
+    lat = U64(0x0A0B) + peel_lanes() * U64(0x0101)
+    is500 = np.zeros(64, bool)
+    for order in (slice(None), slice(None, None, -1)):
+        got = check(make_recs(lat[order], is500, seed=12), q=Q8 + (51 / 64, 52 / 64, 61 / 64))
+        assert got[native.Q_200].tolist() == got[native.Q_ALL].tolist() and got[native.Q_ALL, 0] == 64
+    is500[peel_lanes() == 3] = True   # the class bins: 3 lanes against 61
+    for order in (slice(None), slice(None, None, -1)):
+        got = check(make_recs(lat[order], is500[order], seed=13))
+        assert got[native.Q_500].tolist() == [3] + [0x0A0B + 3 * 0x0101] * len(Q8)
+
+
 @pytest.mark.parametrize("n500", [0, 1])
 def test_rank_boundary(gpu, n500):
     """500 x A then 500 x B: 500000 ppm is the 500th record (A), 500001 ppm the 501st (B)."""

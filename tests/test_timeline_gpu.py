@@ -16,6 +16,7 @@ from oracle import des as od
 from oracle import philox as op
 
 from conftest import TOPOLOGIES
+from test_quantiles_gpu import peel_lanes
 
 pytestmark = pytest.mark.gpu
 
@@ -265,6 +266,31 @@ def test_all_lanes_one_word(gpu, n):
     t = got.reshape(-1, W)
     assert t[124, native.TL_ARRIVED] == n and t[132, native.TL_DONE] == n and t[132, native.TL_SUM_LAT] == n * 8_000_000
     assert t[132, native.TL_MAX_LAT] == 8_000_000 and t[132, native.TL_PROM + 1] == n
+
+
+def peel_case(reverse):
+    """One wave (test_quantiles_gpu.peel_lanes: slot values held by 51, 1, 3, 4 and 5 lanes), every record a
+    200: arrivals in window `slot`, latencies of 8.5 ms + 2 ms * slot (five Prometheus buckets)."""
+    lanes = peel_lanes()[::-1] if reverse else peel_lanes()
+    recs = make_recs(U64(8_500_000) + lanes * U64(2_000_000), 31)
+    recs["status_err"] &= ~BIT31
+    return lanes * U64(1_000_000) + U64(5), recs
+
+
+def test_peel_threshold(gpu):
+    """Multiplicities on both sides of the peel's 'fewer than four' break (csrc/wave_peel.h), in lane order
+    and reversed: in the arrival rows and the histogram words with every completion in the 'after' row of 8
+    windows of 1 ms, then in the completion rows too (one arrival time, 30 windows)."""
+    for reverse in (False, True):
+        arr, recs = peel_case(reverse)
+        got = isim.timeline_table(arr, recs, 10**6, 8, 0)
+        assert np.array_equal(got, expect(arr, recs, 0, 10**6, 8)), reverse
+        t = got.reshape(-1, W)
+        assert t[1:7, native.TL_ARRIVED].tolist() == [51, 1, 0, 3, 4, 5] and t[9, native.TL_DONE] == 64
+        arr[:] = 5
+        got = isim.timeline_table(arr, recs, 10**6, 30, 0)
+        assert np.array_equal(got, expect(arr, recs, 0, 10**6, 30)), reverse
+        assert sorted(got.reshape(-1, W)[:, native.TL_DONE].tolist())[-5:] == [1, 3, 4, 5, 51]
 
 
 @pytest.mark.parametrize("window,n_windows", [(1000, 64), (1 << 20, 1000), (999, 65536)])

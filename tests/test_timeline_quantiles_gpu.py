@@ -16,7 +16,7 @@ from isim import native
 from isim.yamljson import yaml_to_json
 
 from conftest import ROOT, TOPOLOGIES
-from test_timeline_gpu import WINDOWS, arrivals_np, make_case, make_recs, rows_of
+from test_timeline_gpu import WINDOWS, arrivals_np, make_case, make_recs, peel_case, rows_of
 
 pytestmark = pytest.mark.gpu
 
@@ -122,6 +122,24 @@ def test_all_latencies_equal(gpu, n):
         t = check(np.full(n, 123_456_789, U64), recs, 0, 10**6, 200, note=value)
         row = 132 if value == 8_000_000 else 124 if value == 0 else 201
         assert int(t[row, native.Q_ALL, 0]) == n and (t[row, native.Q_ALL, 1:] == U64(value)).all()
+
+
+def test_peel_threshold(gpu):
+    """test_timeline_gpu.peel_case: one wave whose latencies have multiplicities on both sides of the peel's
+    'fewer than four' break (csrc/wave_peel.h), in lane order and reversed.  Every completion in one row (the
+    select's bins; with the 3 lanes of one value as 500s also the (row, code) counters and cursors), then
+    in rows with those multiplicities (counters and cursors)."""
+    q = Q7 + (51 / 64, 52 / 64, 61 / 64)
+    for reverse in (False, True):
+        arr, recs = peel_case(reverse)
+        t = check(arr, recs, 0, 10**6, 8, q, note=reverse)
+        assert t[9, native.Q_200, 0] == 64
+        recs["status_err"][recs["latency_ns"] == 14_500_000] |= BIT31
+        t = check(arr, recs, 0, 10**6, 8, q, note=reverse)
+        assert t[9, :, 0].tolist() == [64, 61, 3]
+        arr[:] = 5
+        t = check(arr, recs, 0, 10**6, 30, q, note=reverse)
+        assert sorted(t[:, native.Q_ALL, 0].tolist())[-5:] == [1, 3, 4, 5, 51]
 
 
 @pytest.mark.parametrize("byte", range(8))

@@ -37,7 +37,7 @@ RESOURCES = {"k_tlq_clear": {"vgprs": 6, "lds_bytes": 0, "scratch_bytes": 0, "wa
              "k_tlq_count": {"vgprs": 32, "lds_bytes": 0, "scratch_bytes": 0, "waves_per_simd": 8},
              "k_tlq_scan": {"vgprs": 36, "lds_bytes": 64, "scratch_bytes": 0, "waves_per_simd": 8},
              "k_tlq_scatter": {"vgprs": 36, "lds_bytes": 0, "scratch_bytes": 0, "waves_per_simd": 8},
-             "k_tlq_select": {"vgprs": 109, "lds_bytes": 79056, "scratch_bytes": 0, "waves_per_simd": 4}}
+             "k_tlq_select": {"vgprs": 111, "lds_bytes": 79056, "scratch_bytes": 0, "waves_per_simd": 4}}
 
 
 def parse():
