@@ -600,6 +600,73 @@ ISIM_API int isim_timeline_quantiles(int device, const uint64_t *h_arrivals, con
                                      uint64_t n, const isim_timeline_params *p, const uint32_t *q_ppm, uint32_t n_q,
                                      uint64_t *h_out);                               /* synchronous convenience */
 
+/* ---- mergeable latency sketch: percentiles across batches, shards and GPUs ----
+ * A log-linear histogram of latency_ns (the HdrHistogram / Fortio kind) whose
+ * every word merges by addition, so that percentiles survive what the exact
+ * selects above cannot: many batches, shards and GPUs, without keeping the
+ * records.  s = sub_bits in 0 .. ISIM_SK_MAX_SUB_BITS refines the bit-length
+ * histogram (s = 0 is ISIM_ST_LOG2 with a bin for 0) by s further bits.
+ *
+ * The bucket rule, exact integer arithmetic for every u64 v (csrc/sketch_bucket.h,
+ * one header for host and device): if v < 2^(s+1), bin = v (the exact region);
+ * otherwise shift = bitlen(v) - (s + 1) and bin = (shift << s) + (v >> shift).
+ * The rule is continuous at 2^(s+1); the last bin, ISIM_SK_BINS(s) - 1, holds
+ * 2^64 - 1.  Bounds of a bin: lo = hi = bin if bin < 2^(s+1); otherwise
+ * shift = (bin >> s) - 1, lo = (2^s + (bin & (2^s - 1))) << shift and
+ * hi = lo + 2^shift - 1, hence hi - lo < lo >> s strictly: at s = 7 a bracket
+ * is narrower than 0.79 % of the value and every latency below 256 ns is exact.
+ *
+ * A table is u64[2][ISIM_SK_BINS(s)], indexed by code (0: a 200, 1: a 500, bit
+ * 31 of status_err) and bin.  It is ACCUMULATED into, like d_stats (zero it
+ * first), and holds counts only, no min or max word: batches fold on the
+ * device by calling again, on the host with isim_sketch_merge, and across GPUs
+ * by a SUM all-reduce of the raw words.
+ *
+ * isim_sketch_quantiles reads one table: out is u64[3][1 + 2 * n_q], by the
+ * classes ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500 (ALL is the sum of the two code
+ * rows).  out[c][0] is the count N_c, out[c][1 + 2i] and out[c][2 + 2i] the lo
+ * and hi of the bin in which the running count first reaches
+ * k = isim_quantile_rank(N_c, q_ppm[i]): the bracket [lo, hi] contains the exact
+ * order statistic.  All words are 0 where N_c is 0.  The quantile list follows
+ * isim_latency_quantiles (1 .. ISIM_MAX_QUANTILES entries, each <= 1,000,000,
+ * any order, repeats allowed); a class count above 2^40 is ISIM_EINVAL.
+ *
+ * isim_latency_sketch_device: one kernel launch on the current device,
+ * asynchronous on hip_stream, no workspace, no host synchronisation, no
+ * allocation, graph-capturable from the first call.  n 0: ISIM_OK, nothing
+ * touched.  ISIM_EINVAL, before any HIP call: sub_bits above
+ * ISIM_SK_MAX_SUB_BITS, a null table, null records with n > 0, n above 2^40,
+ * records not 16-byte or the table not 8-byte aligned.
+ *
+ * isim_timeline_sketch*: one table per row of the timeline (the same
+ * isim_timeline_params, rules and rows as isim_timeline_quantiles: by
+ * COMPLETION, c = arrivals[i] + latency_ns, saturating): out is
+ * u64[n_windows + 2][2][ISIM_SK_BINS(s)], accumulated into; exact for unsorted
+ * arrivals.  The rows summed are the whole-batch table.  Errors: the parameter
+ * errors of isim_timeline*, plus those above (arrivals 8-byte aligned). */
+#define ISIM_SK_MAX_SUB_BITS 7
+#define ISIM_SK_BINS(s) ((uint64_t)(65 - (s)) << (s))          /* 65 at s = 0, 496 at s = 3, 7424 at s = 7 */
+#define ISIM_SK_WORDS(s) (2 * ISIM_SK_BINS(s))                 /* u64 words of one table */
+#define ISIM_SKQ_OUT_WORDS(n_q) (3 * (1 + 2 * (uint64_t)(n_q)))   /* isim_sketch_quantiles' out */
+#define ISIM_TLS_OUT_WORDS(n_windows, s) (((uint64_t)(n_windows) + 2) * ISIM_SK_WORDS(s))
+/* host only, no GPU */
+ISIM_API int isim_sketch_bucket(uint32_t sub_bits, uint64_t v, uint32_t *bin);
+ISIM_API int isim_sketch_bounds(uint32_t sub_bits, uint32_t bin, uint64_t *lo, uint64_t *hi);
+/* dst += src over n_rows tables (n_rows 1 for a whole-batch table, n_windows + 2 for a per-window one) */
+ISIM_API int isim_sketch_merge(uint32_t sub_bits, uint64_t n_rows, uint64_t *dst, const uint64_t *src);
+ISIM_API int isim_sketch_quantiles(uint32_t sub_bits, const uint64_t *table, const uint32_t *q_ppm, uint32_t n_q,
+                                   uint64_t *out);
+ISIM_API int isim_latency_sketch_device(const isim_trace_rec *d_records, uint64_t n, uint32_t sub_bits,
+                                        uint64_t *d_table, void *hip_stream);
+/* Synchronous convenience: host buffers; h_table is accumulated into as well. */
+ISIM_API int isim_latency_sketch(int device, const isim_trace_rec *h_records, uint64_t n, uint32_t sub_bits,
+                                 uint64_t *h_table);
+ISIM_API int isim_timeline_sketch_device(const uint64_t *d_arrivals, const isim_trace_rec *d_records, uint64_t n,
+                                         const isim_timeline_params *p, uint32_t sub_bits, uint64_t *d_out,
+                                         void *hip_stream);
+ISIM_API int isim_timeline_sketch(int device, const uint64_t *h_arrivals, const isim_trace_rec *h_records, uint64_t n,
+                                  const isim_timeline_params *p, uint32_t sub_bits, uint64_t *h_out);
+
 #ifdef __cplusplus
 }
 #endif

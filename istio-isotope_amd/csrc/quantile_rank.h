@@ -1,12 +1,13 @@
 // The nearest-rank rule and the quantile-list rules of the exact percentiles
-// (include/isim.h isim_quantile_rank), shared by quantile.hip
-// and timeline_quantiles.hip.
+// (include/isim.h isim_quantile_rank), shared by quantile.hip,
+// timeline_quantiles.hip and, built by the host compiler, sketch.cpp.
 #pragma once
 
 #include <cstdint>
 #include <string>
 
 #include "../../include/isim.h"
+#include "host_device.h"
 
 namespace isim {
 namespace q {

@@ -17,3 +17,6 @@ from .timeline import (decode_timeline, des_arrivals, des_arrivals_device, des_a
 from .timeline_quantiles import (decode_timeline_quantiles, timeline_quantiles, timeline_quantiles_device,  # noqa: F401
                                  timeline_quantiles_out_words, timeline_quantiles_table,
                                  timeline_quantiles_workspace_bytes)
+from .sketch import (decode_timeline_sketch, latency_sketch, latency_sketch_device, sketch_bins,  # noqa: F401
+                     sketch_bounds, sketch_bucket, sketch_merge, sketch_quantiles, sketch_words, timeline_sketch,
+                     timeline_sketch_device, timeline_sketch_out_words, timeline_sketch_table)

@@ -97,6 +97,15 @@ class DesHandler:
         return timeline_quantiles(self.arrivals(trace_begin, n_traces, device), recs, window_ns, n_windows, t0_ns,
                                   q, device)
 
+    def timeline_sketch(self, trace_begin: int, n_traces: int, window_ns: int, n_windows: int, t0_ns: int = 0,
+                        sub_bits: int = 7, q=DEFAULT_Q, device: int = 0) -> dict:
+        """Serves the batch (as `serve`) and gives per window the mergeable latency sketch of what
+        completes in it, with its quantile brackets: isim.timeline_sketch of its arrivals and records."""
+        from .sketch import timeline_sketch
+        recs, _, _ = self.serve(trace_begin, n_traces, device)
+        return timeline_sketch(self.arrivals(trace_begin, n_traces, device), recs, window_ns, n_windows, t0_ns,
+                               sub_bits, q, device)
+
     def fold(self, table: np.ndarray) -> np.ndarray:
         n = self.handler.info.n_services
         out = np.zeros((max(1, n), native.DES_ROW_WORDS), np.uint64)

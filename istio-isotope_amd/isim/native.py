@@ -58,6 +58,21 @@ Q_ALL, Q_200, Q_500 = 0, 1, 2
 TL_MAX_WINDOWS = 65536
 TL_ARRIVED, TL_DONE, TL_SUM_LAT, TL_MAX_LAT, TL_PROM = 0, 1, 3, 5, 7
 TL_ROW_WORDS = 7 + 2 * N_PROM
+# the mergeable latency sketch (isim.h ISIM_SK_*): a table is u64[2][SK_BINS(s)], by code and bin
+SK_MAX_SUB_BITS = 7
+
+
+def SK_BINS(s: int) -> int:
+    return (65 - s) << s
+
+
+def SK_WORDS(s: int) -> int:
+    return 2 * SK_BINS(s)
+
+
+def SKQ_OUT_WORDS(n_q: int) -> int:
+    """isim_sketch_quantiles' out: u64[3][1 + 2 * n_q], per class the count, then lo and hi per quantile."""
+    return 3 * (1 + 2 * n_q)
 
 
 class IsimError(RuntimeError):
@@ -187,6 +202,14 @@ SIGNATURES = {
                                                  C.c_uint32, _VP, _VP, C.c_uint64, _VP]),
     "isim_timeline_quantiles": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, C.POINTER(TimelineParams),
                                           C.POINTER(C.c_uint32), C.c_uint32, _VP]),
+    "isim_sketch_bucket": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "isim_sketch_bounds": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "isim_sketch_merge": (C.c_int, [C.c_uint32, C.c_uint64, _VP, _VP]),
+    "isim_sketch_quantiles": (C.c_int, [C.c_uint32, _VP, C.POINTER(C.c_uint32), C.c_uint32, _VP]),
+    "isim_latency_sketch_device": (C.c_int, [_VP, C.c_uint64, C.c_uint32, _VP, _VP]),
+    "isim_latency_sketch": (C.c_int, [C.c_int, _VP, C.c_uint64, C.c_uint32, _VP]),
+    "isim_timeline_sketch_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(TimelineParams), C.c_uint32, _VP, _VP]),
+    "isim_timeline_sketch": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, C.POINTER(TimelineParams), C.c_uint32, _VP]),
 }
 
 _lib = None
