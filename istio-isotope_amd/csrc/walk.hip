@@ -458,6 +458,15 @@ __device__ __forceinline__ void count_t(uint64_t *__restrict__ gstats, uint32_t 
   }
 }
 
+// A lane's add to the 500 counter of call site `slot` (LDS table, or global
+// atomics when the table does not fit): the per-chunk count flushes, one lane
+// per record or per close.
+template <bool LDSC>
+__device__ __forceinline__ void site_err_add(const Ctx &c, uint32_t slot, uint32_t v) {
+  if constexpr (LDSC) atomicAdd(c.cnt + c.n_slots + slot, v);
+  else atomicAdd((unsigned long long *)(c.gstats + ISIM_ST_SITES + c.n_slots + slot), (unsigned long long)v);
+}
+
 // Philox4x32-10 of counter (t_lo, t_hi, g, 0); rounds 1-2 fold the
 // wave-uniform words (t_hi when the batch does not straddle 2^32, g, 0) into
 // scalar math.
@@ -546,11 +555,12 @@ __device__ __forceinline__ void philox_lockstep(const uint32_t (&t_lo)[TPL], uin
 // TPL traces per lane: the wave walks 64*TPL traces through one pass over the
 // stream, so the per-record scalar work (fetch, decode, counter adds) is
 // shared and each lane runs TPL independent Philox chains (ILP).
-// BS: mode B keeps the open invocations' statuses in a per-lane bit stack
+// Mode B with a stack of open invocations (mode A: walk_stream_a).
+// BS: the open invocations' statuses in a per-lane bit stack
 // (bit p = running status of the frame at stack position p; VALU), for
 // call depths <= 32 (kernel kind 5); otherwise (kind 4) as wave masks on a
 // VGPR-lane stack.
-template <bool MODEB, bool LDSC, int TPL, bool FULL, bool BS>
+template <bool LDSC, int TPL, bool BS>
 __device__ __forceinline__ void walk_stream(const Ctx &c, CNode4 *__restrict__ stream, uint32_t n_groups,
                                             uint32_t n_nodes, uint64_t t_static, uint64_t trace_begin,
                                             uint64_t n_traces, uint64_t base) {
@@ -606,20 +616,7 @@ __device__ __forceinline__ void walk_stream(const Ctx &c, CNode4 *__restrict__ s
     uint64_t own[TPL];
 #pragma unroll
     for (int u = 0; u < TPL; ++u) own[u] = (meta & 0x80000000u) ? all[u] : (ballot(xw[u] < thr) & all[u]);
-    if constexpr (!MODEB) {
-      // mode A: an invocation's status is its own error draw; padding
-      // records (thr 0, never always) draw nothing.  The root (record 0)
-      // is peeled off before the loop.
-      uint64_t any = 0;
-      uint32_t n = 0;
-#pragma unroll
-      for (int u = 0; u < TPL; ++u) {
-        add_lane(errh[u], own[u]);
-        any |= own[u];
-        n += popc(own[u]);
-      }
-      if (any) count_t<LDSC>(c.gstats, c.cnt, c.n_slots + slot, n, lane0);
-    } else if constexpr (BS) {
+    if constexpr (BS) {
       if (slot == kSlotPad) return;
       uint32_t k = (meta >> 24) & 0x7Fu;
       const uint32_t d = depth;  // this invocation's stack position
@@ -748,32 +745,6 @@ __device__ __forceinline__ void walk_stream(const Ctx &c, CNode4 *__restrict__ s
 #pragma unroll
     for (int u = 0; u < TPL; ++u) x[u][0] = x[u][1] = x[u][2] = x[u][3] = 0;
     draws(q, g, x);
-    if constexpr (!MODEB) {
-      // mode A, no errorRate-1 record in the group: per record one compare
-      // per trace; counts only on the (rarer) records where some lane errs
-      if (((q.n[0].meta | q.n[1].meta | q.n[2].meta | q.n[3].meta) & 0x80000000u) == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          uint64_t own[TPL], any = 0;
-#pragma unroll
-          for (int u = 0; u < TPL; ++u) {
-            own[u] = ballot(x[u][j] < q.n[j].thr);
-            if constexpr (!FULL) own[u] &= all[u];
-            any |= own[u];
-          }
-          if (any) {
-            uint32_t n = 0;
-#pragma unroll
-            for (int u = 0; u < TPL; ++u) {
-              add_lane(errh[u], own[u]);
-              n += popc(own[u]);
-            }
-            count_t<LDSC>(c.gstats, c.cnt, c.n_slots + (q.n[j].meta & 0xFFFFFFu), n, lane0);
-          }
-        }
-        return;
-      }
-    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       uint32_t xw[TPL];
@@ -795,17 +766,7 @@ __device__ __forceinline__ void walk_stream(const Ctx &c, CNode4 *__restrict__ s
       uint32_t xw[TPL];
 #pragma unroll
       for (int u = 0; u < TPL; ++u) xw[u] = x[u][j];
-      if (j == 0 && !MODEB) {
-#pragma unroll
-        for (int u = 0; u < TPL; ++u) {
-          const uint64_t own =
-              (bufA.n[0].meta & 0x80000000u) ? all[u] : (ballot(xw[u] < bufA.n[0].thr) & all[u]);
-          add_lane(errh[u], own);
-          root_st[u] = own;
-        }
-      } else {
-        node(bufA.n[j].thr, bufA.n[j].meta, xw);
-      }
+      node(bufA.n[j].thr, bufA.n[j].meta, xw);
     }
   }
   // Group g+1 is loaded (unconditionally: the device buffer carries two zero
@@ -818,6 +779,156 @@ __device__ __forceinline__ void walk_stream(const Ctx &c, CNode4 *__restrict__ s
     group(cur, g);
     cur = nxt;
   }
+#pragma unroll
+  for (int u = 0; u < TPL; ++u) finish_batch(c, idx[u], valid[u], all[u], t_static, n_nodes, root_st[u], errh[u]);
+}
+
+// Mode A on the draw stream (kernel kind 4): an invocation's status is its own
+// error draw, so per record and trace the vector unit runs one compare and
+// one carried add (the trace's error count) and nothing else.  The record's
+// 500 count is the popcount of its compare masks (scalar), at most 64 TPL, a
+// byte: the four counts of a group are packed into one word and written to
+// lane (g - g0) of a VGPR, one v_writelane per group.  After a chunk of 64
+// groups each lane adds its group's four counts to the records' call sites
+// (its group's records are loaded by vector loads before the chunk's Philox
+// work).  No branch and no LDS operation per record; padding records and the
+// entry (no call site) are dropped at the flush.
+constexpr uint32_t kCountGroups = 64;  // groups per chunk: one lane each
+template <bool LDSC, int TPL, bool FULL>
+__device__ __forceinline__ void walk_stream_a(const Ctx &c, CNode4 *__restrict__ stream, uint32_t n_groups,
+                                              uint32_t n_nodes, uint64_t t_static, uint64_t trace_begin,
+                                              uint64_t n_traces, uint64_t base,
+                                              const uint32_t *__restrict__ stream_w) {
+  static_assert(64 * TPL < 256, "a record's 500 count is packed into a byte");
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const uint32_t lane = lane_id();
+  uint64_t idx[TPL], all[TPL];
+  uint32_t t_lo[TPL], t_hi[TPL], t_hi_u[TPL];
+  bool valid[TPL];
+  bool hi_uniform = true;
+#pragma unroll
+  for (int u = 0; u < TPL; ++u) {
+    idx[u] = base + 64u * u + lane;
+    valid[u] = idx[u] < n_traces;
+    const uint64_t t = trace_begin + idx[u];
+    t_lo[u] = (uint32_t)t;
+    t_hi[u] = (uint32_t)(t >> 32);
+    t_hi_u[u] = rfl(t_hi[u]);
+    hi_uniform = hi_uniform && ballot(t_hi[u] != t_hi_u[u]) == 0 && t_hi_u[u] == t_hi_u[0];  // no 2^32 straddle
+    all[u] = ballot(valid[u]);
+  }
+  uint32_t errh[TPL];
+  uint64_t root_st[TPL];
+#pragma unroll
+  for (int u = 0; u < TPL; ++u) errh[u] = 0;
+  // HU: the batch does not straddle 2^32 (one instantiation of the loop each,
+  // so the test stays out of it); qor: the OR of the group's (thr, meta) pairs
+  auto draws = [&](auto HU, uint64_t qor, uint32_t g, uint32_t (&x)[TPL][4]) {
+#pragma unroll
+    for (int u = 0; u < TPL; ++u) x[u][0] = x[u][1] = x[u][2] = x[u][3] = 0;
+    if ((uint32_t)qor != 0) {
+      if constexpr (decltype(HU)::value) {
+        philox_lockstep<TPL>(t_lo, t_hi_u[0], g, c.k0, c.k1, x);
+      } else {
+#pragma unroll
+        for (int u = 0; u < TPL; ++u) philox_group(t_lo[u], t_hi[u], t_hi_u[u], hi_uniform, g, c.k0, c.k1, x[u]);
+      }
+    }
+  };
+
+  Node4 cur = load_group(stream);
+  {  // record 0 is the entry invocation (the client request): its status is the trace's
+    uint32_t x[TPL][4];
+    if (hi_uniform) draws(std::true_type{}, ~0ull, 0, x);
+    else draws(std::false_type{}, ~0ull, 0, x);
+#pragma unroll
+    for (int u = 0; u < TPL; ++u)
+      root_st[u] = (cur.n[0].meta & 0x80000000u) ? all[u] : (ballot(x[u][0] < cur.n[0].thr) & all[u]);
+  }
+  auto chunks = [&](auto HU) {
+  for (uint32_t g0 = 0; g0 < n_groups; g0 += kCountGroups) {
+    const uint32_t ng = n_groups - g0 < kCountGroups ? n_groups - g0 : kCountGroups;
+    // this lane's group of the chunk (thr, meta of its four records)
+    u32x4 ra = {0u, kSlotPad, 0u, kSlotPad}, rb = ra;
+    if (lane < ng) {
+      const u32x4 *p = reinterpret_cast<const u32x4 *>(stream_w + 8u * (size_t)(g0 + lane));
+      ra = p[0];
+      rb = p[1];
+    }
+    uint32_t pk = 0;  // lane l: the 500 counts of group g0 + l, a byte per record
+    // one group: its Philox blocks, per record and trace the compare and the
+    // carried add, the four counts into the group's lane of pk
+    auto grp = [&](const Node4 &q, uint32_t g) {
+      uint32_t x[TPL][4];
+      uint64_t qor = 0;  // s_or_b64: both tests of the group from three scalar ORs
+#pragma unroll
+      for (int j = 0; j < 4; ++j) qor |= u64of(q.n[j].thr, q.n[j].meta);
+      draws(HU, qor, g, x);
+      {
+        uint64_t own[TPL][4];
+        uint32_t w = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          uint32_t n = 0;
+#pragma unroll
+          for (int u = 0; u < TPL; ++u) {
+            own[u][j] = ballot(x[u][j] < q.n[j].thr);
+            if constexpr (!FULL) own[u][j] &= all[u];
+            add_lane(errh[u], own[u][j]);
+            n += popc(own[u][j]);
+          }
+          w |= n << (8 * j);
+        }
+        // errorRate-1 records (always 500, thr 0: no lane counted above) are
+        // rare: one test per group, a test per record only in the groups
+        // that hold one
+        if ((int64_t)qor < 0) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (!(q.n[j].meta & 0x80000000u)) continue;
+            uint32_t n = 0;
+#pragma unroll
+            for (int u = 0; u < TPL; ++u) {
+              own[u][j] = FULL ? ~0ull : all[u];
+              add_lane(errh[u], own[u][j]);
+              n += popc(own[u][j]);
+            }
+            w |= n << (8 * j);
+          }
+        }
+        pk = wrl(w, g - g0, pk);
+      }
+    };
+    // two groups per trip, each group's records loaded one group ahead into
+    // the other buffer (walk_stream_cl: no register copy between them; the
+    // device buffer carries two zero groups of tail padding)
+    uint32_t g = g0;
+    const uint32_t g1 = g0 + ng;
+    for (; g + 1 < g1; g += 2) {
+      CNode4 *pb = stream + g + 1;
+      asm volatile("" : "+s"(pb) : "s"(cur.n[0].thr));
+      const Node4 b = load_group(pb);
+      grp(cur, g);
+      CNode4 *pc = stream + g + 2;
+      asm volatile("" : "+s"(pc) : "s"(b.n[0].thr));
+      cur = load_group(pc);
+      grp(b, g + 1);
+    }
+    if (g < g1) {
+      const Node4 b = load_group(stream + g + 1);
+      grp(cur, g);
+      cur = b;
+    }
+    const uint32_t slot[4] = {ra.y & 0xFFFFFFu, ra.w & 0xFFFFFFu, rb.y & 0xFFFFFFu, rb.w & 0xFFFFFFu};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t n = (pk >> (8 * j)) & 0xFFu;
+      if (n != 0 && slot[j] < kSlotPad) site_err_add<LDSC>(c, slot[j], n);
+    }
+  }
+  };
+  if (hi_uniform) chunks(std::true_type{});
+  else chunks(std::false_type{});
 #pragma unroll
   for (int u = 0; u < TPL; ++u) finish_batch(c, idx[u], valid[u], all[u], t_static, n_nodes, root_st[u], errh[u]);
 }
@@ -955,10 +1066,7 @@ __device__ __forceinline__ void walk_stream_cl(const Ctx &c, CNode4 *__restrict_
       const uint32_t lm = __builtin_bitreverse32((uint32_t)ballot(leaf)) >> (32u - nrec);  // mb's bit order
 #pragma unroll
       for (int u = 0; u < TPL; ++u) errh[u] += (uint32_t)__builtin_popcount(mb[u] & lm);
-      if (leaf && lcnt) {
-        if constexpr (LDSC) atomicAdd(c.cnt + c.n_slots + rslot, lcnt);
-        else atomicAdd((unsigned long long *)(c.gstats + ISIM_ST_SITES + c.n_slots + rslot), (unsigned long long)lcnt);
-      }
+      if (leaf && lcnt) site_err_add<LDSC>(c, rslot, lcnt);
     }
     const uint32_t ce = close_end[ch];
     CloseBlk blk = load_closes(closes + cp);  // the chunk's first 8 closes
@@ -986,11 +1094,7 @@ __device__ __forceinline__ void walk_stream_cl(const Ctx &c, CNode4 *__restrict_
         }
         blk = nb;
       }
-      if (lane < nseg) {
-        if constexpr (LDSC) atomicAdd(c.cnt + c.n_slots + slotv, cntv);
-        else if (cntv) atomicAdd((unsigned long long *)(c.gstats + ISIM_ST_SITES + c.n_slots + slotv),
-                                 (unsigned long long)cntv);
-      }
+      if (lane < nseg && (LDSC || cntv)) site_err_add<LDSC>(c, slotv, cntv);
       cp += nseg;
       if (cp < ce) slotv = close_slot[cp + lane];  // a chunk with more than 64 closes
     }
@@ -1269,12 +1373,14 @@ __global__ void __launch_bounds__(kWgThreads, KIND >= 4 ? ISIM_STREAM_WAVES : 1)
         else
           walk_stream_cl<LDSC, kStreamTPL, false>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces,
                                                   base, cl, kp.close_slot, ce, (const uint32_t *)prog);
+      } else if constexpr (MODEB) {
+        walk_stream<LDSC, kStreamTPL, KIND == 5>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base);
       } else if (base + 64 * kStreamTPL <= kp.n_traces)  // every lane of every trace slot valid
-        walk_stream<MODEB, LDSC, kStreamTPL, true, KIND == 5>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin,
-                                                   kp.n_traces, base);
+        walk_stream_a<LDSC, kStreamTPL, true>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base,
+                                              (const uint32_t *)prog);
       else
-        walk_stream<MODEB, LDSC, kStreamTPL, false, KIND == 5>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin,
-                                                    kp.n_traces, base);
+        walk_stream_a<LDSC, kStreamTPL, false>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base,
+                                               (const uint32_t *)prog);
     }
     else if constexpr (STATIC) walk_static<MODEB, TT>(c, kp.trace_begin, kp.n_traces, b * 64);
     else walk_dynamic<MODEB, TT>(c, kp.trace_begin, kp.n_traces, b * 64, lstk, hstk);
