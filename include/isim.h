@@ -523,6 +523,84 @@ ISIM_API int isim_des_arrivals_device(const isim_handler *h, const isim_des_para
 ISIM_API int isim_des_arrivals(const isim_handler *h, int device, const isim_des_params *p,
                                uint64_t trace_begin, uint64_t n_traces, uint64_t *h_arrivals);
 
+/* ---- load profiles: steps, spikes, pauses and paced arrivals ----
+ * A time-varying offered load for the DES in place of the one mean of
+ * isim_des_params.  A profile is 1 .. ISIM_LP_MAX_SEGMENTS segments; segment j
+ * lasts duration_ns D_j (1 .. 2^48) at mean_interarrival_ns m_j (0 .. 2^34).
+ * The last segment runs forever: its duration must be 0.  m_j = 0 is a pause
+ * (no arrivals), not allowed as the last segment.  flags is 0 or ISIM_LP_PACED.
+ *
+ * The rule, exact integers (csrc/load_profile.h, one header for host and
+ * device): arrivals are a time change of a unit-rate stream of work in Q24.
+ *   compile  T_0 = C_0 = 0, W_j = floor(D_j 2^24 / m_j) (0 for a pause),
+ *            T_{j+1} = T_j + D_j, C_{j+1} = min(C_j + W_j, 2^63)
+ *   map      for u < 2^63: j = the largest index with C_j <= u,
+ *            t(u) = T_j + floor((u - C_j) m_j / 2^24)   (128-bit product)
+ *   work     of trace i (0-based) of a batch from trace_begin:
+ *            u_i = sum of E(draw_k), k = trace_begin .. trace_begin + i, the
+ *            draws and the Q24 exponential of DESIGN §10.1-§10.2 (no new
+ *            randomness); with ISIM_LP_PACED, u_i = (i + 1) 2^24: evenly paced
+ *            arrivals, one segment of mean m gives A_i = (i + 1) m exactly
+ *   A_i = t(u_i), ns since the batch start, all replicas idle at 0.
+ * t does not decrease in u.  A one-segment profile of mean m floors the sum
+ * where the constant-mean entry points sum the floors:
+ * A_const[i] <= A_profile[i] <= A_const[i] + i + 1; those entry points keep
+ * their arithmetic bit for bit.
+ *
+ * The profile is a host structure, copied at the call.  Every ISIM_EINVAL
+ * below is found before any HIP call: a null profile or segment pointer,
+ * n_segments 0 or above the maximum, unknown flag bits, a duration or mean out
+ * of range, a nonzero last duration, a pause as the last segment; n_traces
+ * above 2^32 (arrivals) or 2^31 (DES); a batch whose horizon, t at the largest
+ * work its traces can reach (n x 24 ln 2 x 2^24, paced n x 2^24), is at or
+ * above 2^62; misaligned buffers; a workspace that is too small.
+ *
+ * isim_load_profile_time is the map on the host (no GPU): ISIM_ERANGE if
+ * work_q24 >= 2^63 or t >= 2^63.
+ *
+ * isim_profile_arrivals* keep the contract of isim_des_arrivals*: any handler
+ * (only its seed is read), n_traces 0 is ISIM_OK with nothing written, the
+ * workspace may be dirty; asynchronous on hip_stream, no host synchronisation,
+ * no allocation, graph-capturable from the first call (the segment table
+ * travels in kernel arguments into the workspace).
+ *
+ * isim_serve_des_profile* keep every contract of isim_serve_des* (accumulation,
+ * ISIM_ST_DES_RETRY, the same workspace of isim_des_workspace_bytes; the
+ * synchronous call reruns with 64-bit rows) with A_i as above; des_flags is 0
+ * or ISIM_DES_FLAG_WIDE.  The segment table lives in the handler's per-device
+ * state: profile batches of one handler on one device must be ordered (one
+ * stream, or events), as calls that share a workspace must.  The first
+ * profile batch of a handler on a device allocates that table (hipMalloc),
+ * so it cannot be captured in a graph under the default capture mode: run one
+ * profile batch before capturing.  A call refused with ISIM_EINVAL has put
+ * nothing on the stream and left the table as it was. */
+#define ISIM_LP_MAX_SEGMENTS 1024u
+#define ISIM_LP_PACED 1u
+typedef struct {
+  uint64_t duration_ns;           /* 1 .. 2^48; the last segment: 0 (forever) */
+  uint64_t mean_interarrival_ns;  /* 0 (a pause) .. 2^34 */
+} isim_load_segment;
+typedef struct {
+  const isim_load_segment *segments;
+  uint32_t n_segments;            /* 1 .. ISIM_LP_MAX_SEGMENTS */
+  uint32_t flags;                 /* 0 or ISIM_LP_PACED */
+} isim_load_profile;
+
+ISIM_API int isim_load_profile_time(const isim_load_profile *lp, uint64_t work_q24, uint64_t *t_ns);  /* host only */
+ISIM_API int isim_profile_arrivals_workspace_bytes(uint64_t n_traces, uint64_t *bytes);                /* host only */
+ISIM_API int isim_profile_arrivals_device(const isim_handler *h, const isim_load_profile *lp, uint64_t trace_begin,
+                                          uint64_t n_traces, uint64_t *d_arrivals, void *d_workspace,
+                                          uint64_t workspace_bytes, void *hip_stream);
+ISIM_API int isim_profile_arrivals(const isim_handler *h, int device, const isim_load_profile *lp,
+                                   uint64_t trace_begin, uint64_t n_traces, uint64_t *h_arrivals);
+ISIM_API int isim_serve_des_profile_device(isim_handler *h, const isim_load_profile *lp, uint32_t des_flags,
+                                           uint64_t trace_begin, uint64_t n_traces, isim_trace_rec *d_records,
+                                           uint64_t *d_stats, uint64_t *d_des_table, void *d_workspace,
+                                           uint64_t workspace_bytes, void *hip_stream);
+ISIM_API int isim_serve_des_profile(isim_handler *h, int device, const isim_load_profile *lp, uint64_t trace_begin,
+                                    uint64_t n_traces, isim_trace_rec *h_records, uint64_t *h_stats,
+                                    uint64_t *h_des_table);
+
 /* Record i arrives at a = arrivals[i] and completes at c = a + latency_ns,
  * saturating at 2^64 - 1.  A time x falls in row 0 ("before") if x < t0_ns;
  * otherwise, with w = floor((x - t0_ns) / window_ns), in row 1 + w if

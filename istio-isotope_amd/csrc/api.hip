@@ -21,6 +21,7 @@
 #include "des.h"
 #include "host_stage.h"
 #include "kernel_abi.h"
+#include "load_profile.h"
 #include "program.h"
 
 namespace {
@@ -99,6 +100,7 @@ struct DevState {
   bool spill_used[isim::kSpillAreas] = {};
   uint32_t spill_next = 0;
   hipMemPool_t des_pool = nullptr;      // the item engine's per-batch arrays (a private pool)
+  isim::lp::Seg *d_lp_table = nullptr;  // load profiles: the segment table of the batch being enqueued (first use)
   bool des_ready = false;               // every DES upload above succeeded (des_prepare)
 };
 
@@ -108,7 +110,8 @@ void free_des(DevState &d) {
   for (void **q : {&d.d_des_pos, (void **)&d.d_des_child, (void **)&d.d_des_level, (void **)&d.d_des_arr,
                    &d.d_des_ext, &d.d_des_steps, (void **)&d.d_des_mult, (void **)&d.d_des_fast,
                    (void **)&d.d_des_sort, (void **)&d.d_des_zero, (void **)&d.d_des_pipe, &d.d_des_ipos,
-                   (void **)&d.d_des_sround, &d.d_des_nodes, &d.d_des_text, &d.d_des_tstep}) {
+                   (void **)&d.d_des_sround, &d.d_des_nodes, &d.d_des_text, &d.d_des_tstep,
+                   (void **)&d.d_lp_table}) {
     if (*q) (void)hipFree(*q);
     *q = nullptr;
   }
@@ -971,6 +974,19 @@ int des_prepare(isim_handler *h, int device, DevState *&st) {
   return ISIM_OK;
 }
 
+// The offered load of one DES batch: a constant mean, or a compiled profile
+// with the batch's horizon (load_profile.h).
+struct DesLoad {
+  uint64_t mean_ns;
+  const isim::lp::Compiled *profile;  // null: mean_ns
+  uint64_t horizon;                   // profile: no arrival of the batch passes it (< 2^62)
+  uint32_t flags;                     // 0 or ISIM_DES_FLAG_WIDE
+};
+
+int serve_des_device(isim_handler *h, const DesLoad &load, uint64_t trace_begin, uint64_t n_traces,
+                     isim_trace_rec *d_records, uint64_t *d_stats, uint64_t *d_des_table, void *d_workspace,
+                     uint64_t workspace_bytes, void *hip_stream);
+
 }  // namespace
 
 extern "C" {
@@ -1021,12 +1037,47 @@ int isim_serve_des_device(isim_handler *h, const isim_des_params *dp, uint64_t t
     return fail(ISIM_EINVAL, "isim_des_params.flags must be 0 or ISIM_DES_FLAG_WIDE, reserved 0");
   if (n_traces == 0) return ISIM_OK;
   if (n_traces > (1ull << 31)) return fail(ISIM_EINVAL, "n_traces above 2^31 per DES batch");
+  const DesLoad load{dp->mean_interarrival_ns, nullptr, 0, dp->flags};
+  return serve_des_device(h, load, trace_begin, n_traces, d_records, d_stats, d_des_table, d_workspace,
+                          workspace_bytes, hip_stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// One DES batch on the current device, the arguments checked by the caller:
+// under load.mean_ns, or under load.profile with its horizon.
+int serve_des_device(isim_handler *h, const DesLoad &load, uint64_t trace_begin, uint64_t n_traces,
+                     isim_trace_rec *d_records, uint64_t *d_stats, uint64_t *d_des_table, void *d_workspace,
+                     uint64_t workspace_bytes, void *hip_stream) {
+  // no arrival of the batch passes this time (an exponential gap is at most 24 ln 2 = 16.6 means)
+  const long double arrival_span =
+      load.profile ? (long double)load.horizon : (long double)n_traces * load.mean_ns * 17.0L;
   int device = 0;
   HIPCHK(hipGetDevice(&device));
   DevState *st = nullptr;
   int rc = des_prepare(h, device, st);
   if (rc != ISIM_OK) return rc;
   const isim::DesPlan &d = h->des;
+  // the profile's table goes up on the stream once every check has passed, just ahead of the batch that
+  // reads it: a refused call leaves the stream and the handler's table as they were
+  isim::lp::DeviceProfile dprof_store{};
+  auto upload_profile = [&](const isim::lp::DeviceProfile *&out) -> int {
+    out = nullptr;
+    if (!load.profile) return ISIM_OK;
+    {
+      std::lock_guard<std::mutex> lk(h->mu);
+      if (!st->d_lp_table &&
+          hipMalloc((void **)&st->d_lp_table, isim::lp::table_bytes(isim::lp::kMaxSegments)) != hipSuccess)
+        return fail(ISIM_EHIP, "hipMalloc(load profile table) failed");
+    }
+    if (isim::lp::upload(*load.profile, st->d_lp_table, hip_stream) != 0)
+      return fail(ISIM_EHIP, "load profile upload failed");
+    dprof_store = {st->d_lp_table, (uint32_t)load.profile->seg.size(), load.profile->paced() ? 1u : 0u};
+    out = &dprof_store;
+    return ISIM_OK;
+  };
   if (d.items) {
     // a dynamic walk: the item engine (des_items.hip); 64-bit times throughout
     if (!d_workspace || workspace_bytes < isim::des_items_workspace_bytes(n_traces))
@@ -1051,13 +1102,14 @@ int isim_serve_des_device(isim_handler *h, const isim_des_params *dp, uint64_t t
     L.d_records = d_records;
     L.n_traces = n_traces;
     L.trace_begin = trace_begin;
-    L.mean_ns = dp->mean_interarrival_ns;
+    L.mean_ns = load.mean_ns;
     L.seed = h->params.seed;
     L.n_slots = (uint32_t)h->prog.n_slots;
     L.flags = h->params.flags;
     L.pool = st->des_pool;
     isim::DesItemsReport rep{};
     L.report = &rep;
+    if (const int urc = upload_profile(L.profile)) return urc;
     std::string e;
     const int irc = isim::des_items_launch(L, hip_stream, e);
     {
@@ -1071,14 +1123,11 @@ int isim_serve_des_device(isim_handler *h, const isim_des_params *dp, uint64_t t
   if (n_traces * (uint64_t)std::max<uint32_t>(1, d.max_sort_pos) > 0xFFFFFFFFull)
     return fail(ISIM_EINVAL, "n_traces x positions of one service above 2^32 per DES batch");
   // the queue scans' keys a_t - t * hold are signed 64-bit (des.hip down passes)
-  if ((long double)n_traces * (long double)d.max_hold +
-          (long double)n_traces * dp->mean_interarrival_ns * 17.0L >= std::ldexp(1.0L, 62))
+  if ((long double)n_traces * (long double)d.max_hold + arrival_span >= std::ldexp(1.0L, 62))
     return fail(ISIM_EINVAL, "DES batch too long for its worker hold times (n_traces x hold above 2^62 ns)");
   if (d.max_rep_bits) {
-    // sort keys hold replica | arrival: the batch's arrival span (an exponential
-    // gap is at most 24 ln 2 = 16.6 means) plus the static latency must fit
-    const long double span = (long double)n_traces * dp->mean_interarrival_ns * 17.0L +
-                             (long double)h->prog.max_latency;
+    // sort keys hold replica | arrival: the batch's arrival span plus the static latency must fit
+    const long double span = arrival_span + (long double)h->prog.max_latency;
     if (span >= std::ldexp(1.0L, 64 - (int)d.max_rep_bits - 1))
       return fail(ISIM_EINVAL, "DES batch too long for the sort keys of a replicated service (arrival span)");
   }
@@ -1104,23 +1153,26 @@ int isim_serve_des_device(isim_handler *h, const isim_des_params *dp, uint64_t t
   L.d_records = d_records;
   L.n_traces = n_traces;
   L.trace_begin = trace_begin;
-  L.mean_ns = dp->mean_interarrival_ns;
+  L.mean_ns = load.mean_ns;
   L.seed = h->params.seed;
   L.stats_words = words;
   L.table_rows = rows;
   L.n_pos = (uint32_t)d.pos.size();
   L.n_slots = (uint32_t)h->prog.n_slots;
   L.modeb = h->params.error_mode == ISIM_MODE_B ? 1u : 0u;
-  L.wide = (dp->flags & ISIM_DES_FLAG_WIDE) != 0;
+  L.wide = (load.flags & ISIM_DES_FLAG_WIDE) != 0;
+  if (const int urc = upload_profile(L.profile)) return urc;
   isim::des_carve(L, d_workspace);
   if (isim::des_launch(L, hip_stream) != 0) return fail(ISIM_EHIP, "DES kernel launch failed");
   return ISIM_OK;
 }
 
-int isim_serve_des(isim_handler *h, int device, const isim_des_params *dp, uint64_t trace_begin, uint64_t n_traces,
-                   isim_trace_rec *h_records, uint64_t *h_stats, uint64_t *h_des_table) {
-  if (!h || !dp) return fail(ISIM_EINVAL, "null argument");
-  if (const int drc = des_ensure(h)) return drc;
+// The synchronous call of both entry points: host buffers, 32-bit rows first
+// and 64-bit rows on retry.  `enqueue` validates one batch's arguments and
+// enqueues it with the given row flags (isim_serve_des_device, or the profile twin).
+template <typename Enqueue>
+int serve_des_host(isim_handler *h, int device, uint32_t flags0, uint64_t n_traces, isim_trace_rec *h_records,
+                   uint64_t *h_stats, uint64_t *h_des_table, Enqueue enqueue) {
   int prev = 0;
   HIPCHK(hipGetDevice(&prev));
   HIPCHK(hipSetDevice(device));
@@ -1145,14 +1197,14 @@ int isim_serve_des(isim_handler *h, int device, const isim_des_params *dp, uint6
       break;
     }
     // 32-bit rows first; a batch they cannot hold (ISIM_ST_DES_RETRY) again with 64-bit rows
-    isim_des_params p = *dp;
+    uint32_t flags = flags0;
     for (int pass = 0; pass < 2; ++pass) {
       if (hipMemsetAsync(d_stats, 0, words * 8, s) != hipSuccess ||
           hipMemsetAsync(d_tab, 0, tab_words * 8 + 8, s) != hipSuccess) {
         rc = fail(ISIM_EHIP, "hipMemset failed");
         break;
       }
-      rc = isim_serve_des_device(h, &p, trace_begin, n_traces, d_rec, d_stats, d_tab, d_ws, ws_bytes + 8, s);
+      rc = enqueue(flags, d_rec, d_stats, d_tab, d_ws, ws_bytes + 8, s);
       if (rc != ISIM_OK) break;
       uint64_t retry = 0;
       if (hipMemcpyAsync(&retry, d_stats + ISIM_ST_DES_RETRY, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -1166,12 +1218,12 @@ int isim_serve_des(isim_handler *h, int device, const isim_des_params *dp, uint6
                              "(device fault flag); the batch was not accumulated");
         break;
       }
-      if ((p.flags & ISIM_DES_FLAG_WIDE) || h->des.items) {
+      if ((flags & ISIM_DES_FLAG_WIDE) || h->des.items) {
         rc = fail(ISIM_EINVAL, "DES batch not accumulated with 64-bit rows: the cyclic schedule found no fixed point "
                                "within 256 passes (or arrivals beyond the sort keys)");
         break;
       }
-      p.flags |= ISIM_DES_FLAG_WIDE;
+      flags |= ISIM_DES_FLAG_WIDE;
     }
     if (rc != ISIM_OK) break;
     if (h_stats && hipMemcpyAsync(h_stats, d_stats, words * 8, hipMemcpyDeviceToHost, s) != hipSuccess) {
@@ -1197,6 +1249,24 @@ int isim_serve_des(isim_handler *h, int device, const isim_des_params *dp, uint6
   if (s) (void)hipStreamDestroy(s);
   (void)hipSetDevice(prev);
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int isim_serve_des(isim_handler *h, int device, const isim_des_params *dp, uint64_t trace_begin, uint64_t n_traces,
+                   isim_trace_rec *h_records, uint64_t *h_stats, uint64_t *h_des_table) {
+  if (!h || !dp) return fail(ISIM_EINVAL, "null argument");
+  if (const int drc = des_ensure(h)) return drc;
+  return serve_des_host(h, device, dp->flags, n_traces, h_records, h_stats, h_des_table,
+                        [&](uint32_t flags, isim_trace_rec *d_rec, uint64_t *d_stats, uint64_t *d_tab, void *d_ws,
+                            uint64_t ws_bytes, hipStream_t s) {
+                          isim_des_params p = *dp;
+                          p.flags = flags;
+                          return isim_serve_des_device(h, &p, trace_begin, n_traces, d_rec, d_stats, d_tab, d_ws,
+                                                       ws_bytes, s);
+                        });
 }
 
 // ---- the arrival times alone (the engine's kernels, des.hip des_arrivals_launch)
@@ -1247,6 +1317,132 @@ int isim_des_arrivals(const isim_handler *h, int device, const isim_des_params *
                                               stage.stream()))
     return rc;
   return stage.download(h_arrivals, d_a, n_traces * 8);
+}
+
+// ---- load profiles (load_profile.h, load_profile.hip)
+static int profile_compile(const isim_load_profile *lp, isim::lp::Compiled &c) {
+  std::string e;
+  const int rc = isim::lp::compile(lp, c, e);
+  return rc == ISIM_OK ? ISIM_OK : fail(rc, e);
+}
+
+// the batch's horizon, or ISIM_EINVAL: the device's sums and products need it below 2^62
+static int profile_horizon(const isim::lp::Compiled &c, uint64_t n_traces, uint64_t &t) {
+  if (!isim::lp::horizon(c, n_traces, t))
+    return fail(ISIM_EINVAL, "load profile: the batch's horizon (the time at the largest work its traces can "
+                             "reach) is at or above 2^62 ns");
+  return ISIM_OK;
+}
+
+int isim_load_profile_time(const isim_load_profile *lp, uint64_t work_q24, uint64_t *t_ns) {
+  if (!t_ns) return fail(ISIM_EINVAL, "null argument");
+  isim::lp::Compiled c;
+  if (const int rc = profile_compile(lp, c)) return rc;
+  if (isim::lp::time_of(c, work_q24, *t_ns) != ISIM_OK)
+    return fail(ISIM_ERANGE, "load profile: work or time at or above 2^63");
+  return ISIM_OK;
+}
+
+// chunk sums, then the segment table (always room for ISIM_LP_MAX_SEGMENTS: the size depends on n alone)
+static uint64_t profile_arrivals_blk_bytes(uint64_t n) { return ((isim::lp::arrival_blocks(n) + 1) * 8 + 255) & ~255ull; }
+static uint64_t profile_arrivals_ws_bytes(uint64_t n) {
+  return profile_arrivals_blk_bytes(n) + ((isim::lp::table_bytes(isim::lp::kMaxSegments) + 255) & ~255ull);
+}
+
+static int profile_arrivals_check(const isim_handler *h, const isim_load_profile *lp, uint64_t n_traces,
+                                  const void *out, isim::lp::Compiled &c) {
+  if (!h) return fail(ISIM_EINVAL, "null argument");
+  if (const int rc = profile_compile(lp, c)) return rc;
+  if (n_traces > isim::lp::kMaxTraces) return fail(ISIM_EINVAL, "n_traces above 2^32 per profile arrivals call");
+  if (n_traces && !out) return fail(ISIM_EINVAL, "null arrivals buffer");
+  uint64_t t;
+  return profile_horizon(c, n_traces, t);
+}
+
+int isim_profile_arrivals_workspace_bytes(uint64_t n_traces, uint64_t *bytes) {
+  if (!bytes) return fail(ISIM_EINVAL, "null argument");
+  if (n_traces > isim::lp::kMaxTraces) return fail(ISIM_EINVAL, "n_traces above 2^32 per profile arrivals call");
+  *bytes = profile_arrivals_ws_bytes(n_traces);
+  return ISIM_OK;
+}
+
+int isim_profile_arrivals_device(const isim_handler *h, const isim_load_profile *lp, uint64_t trace_begin,
+                                 uint64_t n_traces, uint64_t *d_arrivals, void *d_workspace,
+                                 uint64_t workspace_bytes, void *hip_stream) {
+  isim::lp::Compiled c;
+  if (const int rc = profile_arrivals_check(h, lp, n_traces, d_arrivals, c)) return rc;
+  if (n_traces == 0) return ISIM_OK;
+  if (!d_workspace || workspace_bytes < profile_arrivals_ws_bytes(n_traces))
+    return fail(ISIM_EINVAL, "arrivals workspace smaller than isim_profile_arrivals_workspace_bytes()");
+  if (((uintptr_t)d_arrivals & 7u) || ((uintptr_t)d_workspace & 7u))
+    return fail(ISIM_EINVAL, "d_arrivals and d_workspace must be 8-byte aligned");
+  isim::lp::Seg *d_seg = (isim::lp::Seg *)((char *)d_workspace + profile_arrivals_blk_bytes(n_traces));
+  const isim::lp::DeviceProfile dp{d_seg, (uint32_t)c.seg.size(), c.paced() ? 1u : 0u};
+  if (isim::lp::upload(c, d_seg, hip_stream) != 0 ||
+      isim::lp::arrivals_launch(h->params.seed, dp, trace_begin, n_traces, d_arrivals, (uint64_t *)d_workspace,
+                                hip_stream) != 0)
+    return fail(ISIM_EHIP, "profile arrivals kernel launch failed");
+  return ISIM_OK;
+}
+
+int isim_profile_arrivals(const isim_handler *h, int device, const isim_load_profile *lp, uint64_t trace_begin,
+                          uint64_t n_traces, uint64_t *h_arrivals) {
+  isim::lp::Compiled c;
+  if (const int rc = profile_arrivals_check(h, lp, n_traces, h_arrivals, c)) return rc;
+  if (n_traces == 0) return ISIM_OK;
+  const uint64_t ws_bytes = profile_arrivals_ws_bytes(n_traces);
+  isim::HostStage stage(device);
+  void *d_a = stage.alloc(n_traces * 8), *d_ws = stage.alloc(ws_bytes);
+  if (stage.rc() != ISIM_OK) return stage.rc();
+  if (const int rc = isim_profile_arrivals_device(h, lp, trace_begin, n_traces, (uint64_t *)d_a, d_ws, ws_bytes,
+                                                  stage.stream()))
+    return rc;
+  return stage.download(h_arrivals, d_a, n_traces * 8);
+}
+
+// the checks both DES profile entry points share, all on the host
+static int profile_des_check(isim_handler *h, const isim_load_profile *lp, uint32_t des_flags, uint64_t n_traces,
+                             isim::lp::Compiled &c, DesLoad &load) {
+  if (!h) return fail(ISIM_EINVAL, "null argument");
+  if (const int rc = profile_compile(lp, c)) return rc;
+  if (des_flags & ~ISIM_DES_FLAG_WIDE) return fail(ISIM_EINVAL, "des_flags must be 0 or ISIM_DES_FLAG_WIDE");
+  if (n_traces > (1ull << 31)) return fail(ISIM_EINVAL, "n_traces above 2^31 per DES batch");
+  load = DesLoad{0, &c, 0, des_flags};
+  return profile_horizon(c, n_traces, load.horizon);
+}
+
+int isim_serve_des_profile_device(isim_handler *h, const isim_load_profile *lp, uint32_t des_flags,
+                                  uint64_t trace_begin, uint64_t n_traces, isim_trace_rec *d_records,
+                                  uint64_t *d_stats, uint64_t *d_des_table, void *d_workspace,
+                                  uint64_t workspace_bytes, void *hip_stream) {
+  isim::lp::Compiled c;
+  DesLoad load{};
+  if (const int rc = profile_des_check(h, lp, des_flags, n_traces, c, load)) return rc;
+  if (!d_stats || !d_des_table) return fail(ISIM_EINVAL, "null argument");
+  if (n_traces == 0) return ISIM_OK;
+  if (((uintptr_t)d_stats & 7u) || ((uintptr_t)d_des_table & 7u) || ((uintptr_t)d_workspace & 7u) ||
+      ((uintptr_t)d_records & 15u))
+    return fail(ISIM_EINVAL, "d_stats, d_des_table and d_workspace must be 8-byte, d_records 16-byte aligned");
+  uint64_t need = 0;
+  if (const int rc = isim_des_workspace_bytes(h, n_traces, &need)) return rc;
+  if (!d_workspace || workspace_bytes < need)
+    return fail(ISIM_EINVAL, "DES workspace smaller than isim_des_workspace_bytes()");
+  return serve_des_device(h, load, trace_begin, n_traces, d_records, d_stats, d_des_table, d_workspace,
+                          workspace_bytes, hip_stream);
+}
+
+int isim_serve_des_profile(isim_handler *h, int device, const isim_load_profile *lp, uint64_t trace_begin,
+                           uint64_t n_traces, isim_trace_rec *h_records, uint64_t *h_stats, uint64_t *h_des_table) {
+  isim::lp::Compiled c;
+  DesLoad load{};
+  if (const int rc = profile_des_check(h, lp, 0, n_traces, c, load)) return rc;
+  if (const int drc = des_ensure(h)) return drc;
+  return serve_des_host(h, device, 0, n_traces, h_records, h_stats, h_des_table,
+                        [&](uint32_t flags, isim_trace_rec *d_rec, uint64_t *d_stats, uint64_t *d_tab, void *d_ws,
+                            uint64_t ws_bytes, hipStream_t s) {
+                          return isim_serve_des_profile_device(h, lp, flags, trace_begin, n_traces, d_rec, d_stats,
+                                                               d_tab, d_ws, ws_bytes, s);
+                        });
 }
 
 void isim_debug_set_spin_limit(uint32_t polls) { isim::des_set_spin_limit(polls); }

@@ -185,6 +185,12 @@ struct DesBufs {
   void *sort_tmp;                    // rocPRIM's temporary storage
 };
 
+// A load profile on the device (load_profile.h); both engines take one in
+// place of the constant mean.
+namespace lp {
+struct DeviceProfile;
+}
+
 // Device buffers and sizes of one DES batch (des.hip: des_launch).
 struct DesLaunch {
   const DesPlan *plan;               // host copy (the schedule)
@@ -201,6 +207,7 @@ struct DesLaunch {
   uint32_t table_rows;
   uint32_t n_pos, n_slots, modeb;
   bool wide;                         // u64 rows (ISIM_DES_FLAG_WIDE); else u32 rows + overflow retry
+  const lp::DeviceProfile *profile;  // the arrivals follow it (null: the constant mean_ns)
 };
 
 // Workspace bytes for a batch of n traces: a sizing run of des_layout (des_layout.h).
@@ -259,6 +266,7 @@ struct DesItemsLaunch {
   uint32_t flags;  // isim_params.flags (ISIM_FLAG_DES_*: the independent-check paths)
   void *pool;  // hipMemPool_t
   DesItemsReport *report;  // filled when the batch ends (null: none)
+  const lp::DeviceProfile *profile;  // the arrivals follow it (null: the constant mean_ns)
 };
 uint64_t des_items_workspace_bytes(uint64_t n);
 int des_items_launch(const DesItemsLaunch &L, void *stream, std::string &err);

@@ -55,6 +55,7 @@
 
 #include "des_layout.h"
 #include "kernel_abi.h"
+#include "load_profile.h"
 #include "tree_walk.h"
 
 namespace isim {
@@ -1568,10 +1569,16 @@ struct Batch {
 
   // 1. arrivals
   int arrivals() {
-    hipLaunchKernelGGL(k_gaps, dim3(grid_for(n)), dim3(kT), 0, s, k);
+    // under a load profile the gaps are work (Q24) and the scan's sums are mapped to times in place
+    if (L.profile) {
+      if (lp::work_launch(L.seed, *L.profile, L.trace_begin, n, k.gap, s)) return fail("profile work");
+    } else {
+      hipLaunchKernelGGL(k_gaps, dim3(grid_for(n)), dim3(kT), 0, s, k);
+    }
     size_t b = scan_bytes;
     if (rocprim::inclusive_scan(T.scan_tmp, b, k.gap, k.A, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess)
       return fail("arrival scan");
+    if (L.profile && lp::map_launch(*L.profile, n, k.A, s)) return fail("profile map");
     return 0;
   }
 

@@ -10,6 +10,8 @@ from .sim import REC_DTYPE, Handler, SimParams, decode_stats, handler_from_servi
 from .yamljson import yaml_to_json  # noqa: F401
 from . import prometheus  # noqa: F401
 from .des import DesHandler  # noqa: F401
+from .load_profile import (LoadProfile, profile_arrivals, profile_arrivals_device,  # noqa: F401
+                           profile_arrivals_workspace_bytes)
 from .quantiles import (DEFAULT_Q, latency_quantiles, latency_quantiles_device, quantile_rank,  # noqa: F401
                         quantiles_out_words, quantiles_workspace_bytes)
 from .timeline import (decode_timeline, des_arrivals, des_arrivals_device, des_arrivals_workspace_bytes,  # noqa: F401

@@ -1,6 +1,7 @@
 """Per-replica worker-pool DES (BASELINE config 5).
 
     d = DesHandler(handler, mean_interarrival_ns=6_000_000)
+    d = DesHandler(handler, profile=isim.LoadProfile.steps([...], then_mean_ns))   # a time-varying load (§17)
     recs, stats, table = d.serve(trace_begin, n_traces, device=0)
     rows = d.fold(table)      # [n_services][DES_ROW_WORDS]
 
@@ -29,9 +30,14 @@ from .sim import REC_DTYPE, Handler
 
 
 class DesHandler:
-    def __init__(self, handler: Handler, mean_interarrival_ns: int):
+    def __init__(self, handler: Handler, mean_interarrival_ns: int = None, profile=None):
+        """Exactly one of mean_interarrival_ns (a stationary Poisson load) and
+        profile (an isim.LoadProfile) is given."""
+        if (mean_interarrival_ns is None) == (profile is None):
+            raise ValueError("DesHandler takes exactly one of mean_interarrival_ns and profile")
         self.handler = handler
-        self.params = native.DesParams(int(mean_interarrival_ns), 0, 0)
+        self.profile = profile
+        self.params = native.DesParams(int(mean_interarrival_ns), 0, 0) if profile is None else None
         info = native.DesInfo()
         native.check(native.load().isim_des_info_get(handler._h, C.byref(info)))
         self.info = info
@@ -60,6 +66,12 @@ class DesHandler:
         stats = self.handler.new_stats()
         table = self.new_table()
         recs = np.zeros(n_traces, REC_DTYPE) if records else None
+        if self.profile is not None:
+            # isim_serve_des_profile starts with 32-bit rows and reruns wide itself: `wide` changes no result
+            native.check(native.load().isim_serve_des_profile(
+                self.handler._h, device, self.profile.c, trace_begin, n_traces,
+                recs.ctypes.data if records and n_traces else None, stats.ctypes.data, table.ctypes.data))
+            return recs, stats, table
         p = native.DesParams(self.params.mean_interarrival_ns, native.DES_FLAG_WIDE if wide else 0, 0)
         native.check(native.load().isim_serve_des(
             self.handler._h, device, C.byref(p), trace_begin, n_traces,
@@ -68,6 +80,11 @@ class DesHandler:
 
     def serve_device(self, trace_begin: int, n_traces: int, d_records: int, d_stats: int, d_table: int,
                      d_workspace: int, workspace_bytes: int, stream: int = 0, wide: bool = False) -> None:
+        if self.profile is not None:
+            native.check(native.load().isim_serve_des_profile_device(
+                self.handler._h, self.profile.c, native.DES_FLAG_WIDE if wide else 0, trace_begin, n_traces,
+                d_records or None, d_stats, d_table, d_workspace, workspace_bytes, stream or None))
+            return
         p = self.params
         if wide:
             p = native.DesParams(p.mean_interarrival_ns, native.DES_FLAG_WIDE, 0)
@@ -77,6 +94,9 @@ class DesHandler:
 
     def arrivals(self, trace_begin: int, n_traces: int, device: int = 0) -> np.ndarray:
         """The arrival times (u64 ns since batch start) `serve` uses for these traces."""
+        if self.profile is not None:
+            from .load_profile import profile_arrivals
+            return profile_arrivals(self.handler, self.profile, trace_begin, n_traces, device)
         from .timeline import des_arrivals
         return des_arrivals(self.handler, self.params.mean_interarrival_ns, trace_begin, n_traces, device)
 

@@ -60,6 +60,9 @@ TL_ARRIVED, TL_DONE, TL_SUM_LAT, TL_MAX_LAT, TL_PROM = 0, 1, 3, 5, 7
 TL_ROW_WORDS = 7 + 2 * N_PROM
 # the mergeable latency sketch (isim.h ISIM_SK_*): a table is u64[2][SK_BINS(s)], by code and bin
 SK_MAX_SUB_BITS = 7
+# load profiles (isim.h ISIM_LP_*)
+LP_MAX_SEGMENTS = 1024
+LP_PACED = 1
 
 
 def SK_BINS(s: int) -> int:
@@ -110,6 +113,14 @@ class LaunchInfo(C.Structure):
 
 class DesParams(C.Structure):
     _fields_ = [("mean_interarrival_ns", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LoadSegment(C.Structure):
+    _fields_ = [("duration_ns", C.c_uint64), ("mean_interarrival_ns", C.c_uint64)]
+
+
+class LoadProfile(C.Structure):
+    _fields_ = [("segments", C.POINTER(LoadSegment)), ("n_segments", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class TimelineParams(C.Structure):
@@ -194,6 +205,15 @@ SIGNATURES = {
     "isim_des_arrivals_device": (C.c_int, [_VP, C.POINTER(DesParams), C.c_uint64, C.c_uint64, _VP, _VP, C.c_uint64,
                                            _VP]),
     "isim_des_arrivals": (C.c_int, [_VP, C.c_int, C.POINTER(DesParams), C.c_uint64, C.c_uint64, _VP]),
+    "isim_load_profile_time": (C.c_int, [C.POINTER(LoadProfile), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "isim_profile_arrivals_workspace_bytes": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "isim_profile_arrivals_device": (C.c_int, [_VP, C.POINTER(LoadProfile), C.c_uint64, C.c_uint64, _VP, _VP,
+                                               C.c_uint64, _VP]),
+    "isim_profile_arrivals": (C.c_int, [_VP, C.c_int, C.POINTER(LoadProfile), C.c_uint64, C.c_uint64, _VP]),
+    "isim_serve_des_profile_device": (C.c_int, [_VP, C.POINTER(LoadProfile), C.c_uint32, C.c_uint64, C.c_uint64, _VP,
+                                                _VP, _VP, _VP, C.c_uint64, _VP]),
+    "isim_serve_des_profile": (C.c_int, [_VP, C.c_int, C.POINTER(LoadProfile), C.c_uint64, C.c_uint64, _VP, _VP,
+                                         _VP]),
     "isim_timeline_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(TimelineParams), _VP, _VP]),
     "isim_timeline": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, C.POINTER(TimelineParams), _VP]),
     "isim_timeline_merge": (C.c_int, [C.c_uint32, _VP, _VP]),
