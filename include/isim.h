@@ -197,7 +197,11 @@ typedef struct {
                                 6 draw stream with the mode-B close list (ISIM_FLAG_CLOSE_LIST, or a stream
                                 too long for kind 8's LDS mark table),
                                 7 lane tree walk (dynamic walks whose unrolled tree of potential
-                                invocations has at most 2^24 positions; else 2/3),
+                                invocations has at most 2^24 positions, or the site graph, tree_wide 2;
+                                every single figure of a position must stay below 2^32 ns — a call's
+                                hop cost, a script's sleeps between two call steps or after the last,
+                                the longest sleep of a concurrent step — though the latency bound may
+                                pass it, and at most 65 calling invocations may nest; else 2/3),
                                 8 draw stream with mode-B sparse ancestor marking (the default in mode B) */
   int32_t fill;              /* 1: a draw-free static walk: one trace walked, batches are a record fill
                                 (isim_fill_const) + n x its statistics (off with ISIM_FLAG_WALK_ALL) */

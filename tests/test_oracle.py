@@ -212,9 +212,14 @@ def random_graph(draw):
 @given(random_graph(), st.sampled_from([0, 1]), st.integers(0, 2 ** 64 - 1), st.integers(0, 2 ** 40))
 def test_python_vs_c_executor(j, mode, seed, begin):
     sg = ex.SimGraph(gr.unmarshal_service_graph(j))
-    p = ex.SimParams(seed=seed, error_mode=mode)
-    recs, st_ = ex.run(sg, p, 0, begin, 40)
-    crec, cst = oc.run(sg, p, 0, begin, 40)
+    assert_python_equals_c(sg, ex.SimParams(seed=seed, error_mode=mode), begin, 40)
+
+
+def assert_python_equals_c(sg, p, begin, n):
+    """The pure-Python executor and the C executor on traces [begin, begin + n)
+    of the entry s0: records, counters, duration table and histograms."""
+    recs, st_ = ex.run(sg, p, 0, begin, n)
+    crec, cst = oc.run(sg, p, 0, begin, n)
     assert [r[0] for r in recs] == [int(x) for x in crec[:, 0]]
     assert [r[1] | ((r[2] << 31 | r[3]) << 32) for r in recs] == [int(x) for x in crec[:, 1]]
     cs = oc.split_stats(cst, len(sg.g.services), len(sg.sites))
