@@ -93,7 +93,8 @@ typedef struct {
 #define ISIM_FLAG_NO_SVC_DUR 2u /* dynamic walks: do not record per-service invocation durations */
 #define ISIM_FLAG_WALK_ALL 4u   /* draw-free static walks: walk every trace (default: walk one, fill the rest) */
 #define ISIM_FLAG_BIT_STACK 8u  /* mode B on the draw stream: the bit-stack kernel (kind 5, call depth <= 32;
-                                   kind 4 deeper) instead of the close-list kernel (kind 6) */
+                                   kind 4 deeper) instead of sparse ancestor marking (kind 8, the default) or
+                                   the close-list kernel (kind 6) */
 #define ISIM_FLAG_DYNAMIC 16u   /* treat every walk as dynamic: the general kernels with per-lane time and hop
                                    ids (kind 7, or 2/3) even when every trace executes the same invocations
                                    (parity tests of the general path on static graphs; no DES) */

@@ -172,7 +172,7 @@ struct isim_handler {
 
 namespace {
 
-// Kernel kinds 4-6 walk the draw stream (static walks).
+// Kernel kinds 4, 5, 6 and 8 walk the draw stream (static walks); 7 is the lane tree walk.
 bool is_stream(uint32_t kind) { return (kind >= 4 && kind <= 6) || kind == 8; }
 
 // Rows of the device per-service duration table (dynamic walks only).

@@ -265,6 +265,7 @@ constexpr uint32_t kHistWords = 2 * ISIM_N_PROM + 2 * ISIM_N_LOG2;
 // walk.hip: kernel pointer for a walk variant.
 // kind: 0/1 static interpreter u32/u64 time, 2/3 dynamic u32/u64, 4 draw stream,
 // 5 draw stream + mode-B bit stack, 6 draw stream + mode-B close list,
+// 8 draw stream + mode-B sparse ancestor marking (4, 5, 6, 8: stream_walk.h),
 // 7 lane tree walk (dynamic walks, tree.hip; `frames` = register stack depth).
 void *walk_kernel(int kind, bool modeb, bool lds_counters);
 // kind 7 variant (tree.hip, compiled once per mode and concurrency):

@@ -1,4 +1,4 @@
-"""GPU parity of the draw-stream walks' per-record tail (walk.hip): the
+"""GPU parity of the draw-stream walks' per-record tail (stream_walk.h): the
 per-site 500 counts collected per chunk instead of per record, the per-trace
 error count, the errorRate-1 and all-zero-threshold groups, ragged and
 2^32-straddling batches.  Records and stats bit-exact against the C oracle,
@@ -129,6 +129,14 @@ def test_trace_ids_straddle_2_32(gpu, variant):
     # t_hi differs inside the first wave and between the two
     c = _case(_chain(22, 2), variant)
     c.compare((1 << 32) - 64, 256)
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_ragged_batch_straddles_2_32(gpu, variant):
+    # one wave, 100 of its 128 trace slots valid, t_hi differing inside it:
+    # the ragged walk together with the per-trace (not lockstep) draws
+    c = _case(_chain(22, 2), variant)
+    c.compare((1 << 32) - 30, 100)
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
