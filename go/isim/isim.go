@@ -203,6 +203,58 @@ func (h *Handler) DesArrivals(device int, begin uint64, meanGapNs uint64, n int)
 	return out, lastErr(rc)
 }
 
+// ClosedLoop is the reference's load client (Fortio's connections and qps):
+// each of Connections sends its next request when the previous response has
+// arrived and, with PeriodNs > 0, not before its slot (isim.h, DESIGN §18).
+type ClosedLoop struct {
+	Connections uint32
+	PeriodNs    uint64 // per connection; 0 is qps "max"
+	Uniform     bool   // stagger the connections' slots (Fortio's -uniform)
+}
+
+// ClosedLoopInfo is the info block of a closed-loop batch.
+type ClosedLoopInfo struct {
+	MakespanNs, MinFreeNs, Late, SumLateNs uint64
+}
+
+func (c ClosedLoop) batch(recs []TraceRecord, firstIndex uint64, freeAt []uint64,
+	call func(*C.struct_isim_closed_loop, *TraceRecord, *C.uint64_t, *C.uint64_t, *C.uint64_t) C.int) ([]uint64, ClosedLoopInfo, error) {
+	if freeAt != nil && len(freeAt) != int(c.Connections) {
+		return nil, ClosedLoopInfo{}, errors.New("freeAt must hold one value per connection")
+	}
+	p := C.struct_isim_closed_loop{connections: C.uint32_t(c.Connections), period_ns: C.uint64_t(c.PeriodNs),
+		first_index: C.uint64_t(firstIndex)}
+	if c.Uniform {
+		p.flags = C.ISIM_CL_UNIFORM
+	}
+	var rp *TraceRecord
+	if len(recs) > 0 {
+		rp = &recs[0]
+	}
+	arrivals := make([]uint64, len(recs))
+	info := make([]uint64, C.ISIM_CL_INFO_WORDS)
+	rc := call(&p, rp, u64ptr(freeAt), u64ptr(arrivals), u64ptr(info))
+	return arrivals, ClosedLoopInfo{info[C.ISIM_CL_MAKESPAN], info[C.ISIM_CL_MIN_FREE], info[C.ISIM_CL_LATE],
+		info[C.ISIM_CL_SUM_LATE]}, lastErr(rc)
+}
+
+// Arrivals returns the arrival times of recs as requests firstIndex.. of the
+// run, on GPU `device` (isim_closed_loop).  freeAt, one value per connection,
+// is read and overwritten with the state after the batch; nil starts a run
+// and returns no state.
+func (c ClosedLoop) Arrivals(device int, recs []TraceRecord, firstIndex uint64, freeAt []uint64) ([]uint64, ClosedLoopInfo, error) {
+	return c.batch(recs, firstIndex, freeAt, func(p *C.struct_isim_closed_loop, r *TraceRecord, f, a, i *C.uint64_t) C.int {
+		return C.isim_closed_loop(C.int(device), p, r, C.uint64_t(len(recs)), f, a, i)
+	})
+}
+
+// ArrivalsHost is Arrivals on the host, without a GPU (isim_closed_loop_host).
+func (c ClosedLoop) ArrivalsHost(recs []TraceRecord, firstIndex uint64, freeAt []uint64) ([]uint64, ClosedLoopInfo, error) {
+	return c.batch(recs, firstIndex, freeAt, func(p *C.struct_isim_closed_loop, r *TraceRecord, f, a, i *C.uint64_t) C.int {
+		return C.isim_closed_loop_host(p, r, C.uint64_t(len(recs)), f, a, i)
+	})
+}
+
 // TimelineRow is one row of a timeline table: the requests that arrived in
 // the window and, of those that completed in it, by code (0: 200, 1: 500),
 // their count, latency sum, latency maximum and Prometheus histogram.

@@ -750,6 +750,82 @@ ISIM_API int isim_timeline_sketch_device(const uint64_t *d_arrivals, const isim_
 ISIM_API int isim_timeline_sketch(int device, const uint64_t *h_arrivals, const isim_trace_rec *h_records, uint64_t n,
                                   const isim_timeline_params *p, uint32_t sub_bits, uint64_t *h_out);
 
+/* ---- closed-loop clients: connection-limited arrivals for every walk (EXT) ----
+ * The reference's load client (Fortio: num_concurrent_connections, qps) is a
+ * closed loop: each of C connections sends its next request only when the
+ * previous response has arrived and, with a numeric qps, never before its paced
+ * slot.  For a walk a trace's latency does not depend on when it starts, so the
+ * arrival times of a batch of finished records are an exact integer recurrence
+ * along each connection.  The result is a u64 arrivals[n], which isim_timeline*,
+ * isim_timeline_quantiles* and isim_timeline_sketch* take as it is.
+ *
+ * A client has `connections` C (1 .. ISIM_CL_MAX_CONNECTIONS) and a period
+ * p = period_ns per connection (0: "max", no pacing; else 1 .. 2^40).  flags is
+ * 0 or ISIM_CL_UNIFORM (the connections' slots staggered, Fortio's -uniform).
+ * A run is a sequence of requests j = 0, 1, 2, ...; a batch covers requests
+ * first_index .. first_index + n - 1 (first_index <= 2^40, n <= 2^32); request
+ * first_index + i is record i.  The rule (csrc/closed_loop.h, one header for
+ * host and device):
+ *   c = j mod C,  k = j div C                    connection and its k-th request
+ *   o_c = floor(c p / C) with ISIM_CL_UNIFORM, else 0
+ *   s_j = o_c + k p                              scheduled start
+ *   A_j = max(F_c, s_j)                          actual start: arrivals[i]
+ *   F_c <- A_j + latency_ns(record i)            connection c is free again
+ * Every addition saturates at 2^64 - 1 (as the timeline's completion time), so
+ * the rule is defined for every u64 latency.  F is the state u64 free_at[C]:
+ * read at the call, overwritten with the state after the batch; a connection
+ * with no request in the batch keeps its value; all zeros starts a run; a null
+ * pointer means zeros in and nothing out.  Successive batches with consecutive
+ * first_index that pass the state along equal one big batch, value for value.
+ * Request j is the map x -> max(x + L_j, s_j + L_j); (a1, b1) followed by
+ * (a2, b2) composes to (a1 + a2, max(b1 + a2, b2)), which is associative under
+ * saturation, so the device's scan along each connection is exact.
+ *
+ * info is u64[ISIM_CL_INFO_WORDS], WRITTEN (not accumulated): the max and the
+ * min of free_at over all C connections after the batch, the number of requests
+ * of the batch with A_j > s_j and the sum of A_j - s_j mod 2^64 (coordinated
+ * omission).  The achieved rate of a run is requests / makespan.
+ *
+ * ISIM_EINVAL, always before any HIP call: a null client, info or (n > 0)
+ * records or arrivals pointer; connections 0 or above the maximum; unknown
+ * flags; a period above 2^40; first_index above 2^40; n above 2^32; a batch
+ * whose last scheduled start o_c + k_max p, k_max = (first_index + n - 1) div C,
+ * would reach 2^63; records not 16-byte aligned, the other buffers not 8-byte
+ * aligned; a null or too small workspace (n > 0).
+ *
+ * isim_closed_loop_device keeps the contract of isim_latency_quantiles_device:
+ * asynchronous on hip_stream, no host synchronisation, no allocation,
+ * graph-capturable from the first call; the workspace may be dirty (calls that
+ * share one must be ordered).  n 0: ISIM_OK, info written from the incoming
+ * state, everything else untouched (no workspace needed). */
+#define ISIM_CL_MAX_CONNECTIONS 65536u
+#define ISIM_CL_UNIFORM 1u
+#define ISIM_CL_MAKESPAN 0   /* max of free_at after the batch */
+#define ISIM_CL_MIN_FREE 1   /* min of free_at after the batch */
+#define ISIM_CL_LATE     2   /* requests of the batch with A_j > s_j */
+#define ISIM_CL_SUM_LATE 3   /* sum of A_j - s_j, mod 2^64 */
+#define ISIM_CL_INFO_WORDS 4
+/* a struct tag, not a typedef: the synchronous entry point bears the same name */
+struct isim_closed_loop {
+  uint32_t connections;   /* 1 .. ISIM_CL_MAX_CONNECTIONS */
+  uint32_t flags;         /* 0 or ISIM_CL_UNIFORM */
+  uint64_t period_ns;     /* 0 ("max") or 1 .. 2^40, per connection */
+  uint64_t first_index;   /* the run's index of record 0, <= 2^40 */
+};
+
+/* host only, no GPU: request j's connection and scheduled start (first_index is not read) */
+ISIM_API int isim_closed_loop_schedule(const struct isim_closed_loop *cl, uint64_t j, uint32_t *c, uint64_t *s_ns);
+/* host only, no GPU: the rule as a plain sequential loop */
+ISIM_API int isim_closed_loop_host(const struct isim_closed_loop *cl, const isim_trace_rec *h_records, uint64_t n,
+                                   uint64_t *h_free_at, uint64_t *h_arrivals, uint64_t *h_info);
+ISIM_API int isim_closed_loop_workspace_bytes(uint64_t n, uint32_t connections, uint64_t *bytes);  /* host only */
+ISIM_API int isim_closed_loop_device(const struct isim_closed_loop *cl, const isim_trace_rec *d_records, uint64_t n,
+                                     uint64_t *d_free_at, uint64_t *d_arrivals, uint64_t *d_info,
+                                     void *d_workspace, uint64_t workspace_bytes, void *hip_stream);
+/* Synchronous convenience: host buffers (h_free_at may be NULL). */
+ISIM_API int isim_closed_loop(int device, const struct isim_closed_loop *cl, const isim_trace_rec *h_records, uint64_t n,
+                              uint64_t *h_free_at, uint64_t *h_arrivals, uint64_t *h_info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ from . import prometheus  # noqa: F401
 from .des import DesHandler  # noqa: F401
 from .load_profile import (LoadProfile, profile_arrivals, profile_arrivals_device,  # noqa: F401
                            profile_arrivals_workspace_bytes)
+from .closed_loop import (ClosedLoop, ClosedLoopRun, closed_loop_workspace_bytes,  # noqa: F401
+                          decode_closed_loop_info)
 from .quantiles import (DEFAULT_Q, latency_quantiles, latency_quantiles_device, quantile_rank,  # noqa: F401
                         quantiles_out_words, quantiles_workspace_bytes)
 from .timeline import (decode_timeline, des_arrivals, des_arrivals_device, des_arrivals_workspace_bytes,  # noqa: F401

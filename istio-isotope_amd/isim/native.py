@@ -63,6 +63,11 @@ SK_MAX_SUB_BITS = 7
 # load profiles (isim.h ISIM_LP_*)
 LP_MAX_SEGMENTS = 1024
 LP_PACED = 1
+# closed-loop clients (isim.h ISIM_CL_*): info is u64[CL_INFO_WORDS]
+CL_MAX_CONNECTIONS = 65536
+CL_UNIFORM = 1
+CL_MAKESPAN, CL_MIN_FREE, CL_LATE, CL_SUM_LATE = 0, 1, 2, 3
+CL_INFO_WORDS = 4
 
 
 def SK_BINS(s: int) -> int:
@@ -121,6 +126,11 @@ class LoadSegment(C.Structure):
 
 class LoadProfile(C.Structure):
     _fields_ = [("segments", C.POINTER(LoadSegment)), ("n_segments", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ClosedLoop(C.Structure):
+    _fields_ = [("connections", C.c_uint32), ("flags", C.c_uint32), ("period_ns", C.c_uint64),
+                ("first_index", C.c_uint64)]
 
 
 class TimelineParams(C.Structure):
@@ -230,6 +240,13 @@ SIGNATURES = {
     "isim_latency_sketch": (C.c_int, [C.c_int, _VP, C.c_uint64, C.c_uint32, _VP]),
     "isim_timeline_sketch_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(TimelineParams), C.c_uint32, _VP, _VP]),
     "isim_timeline_sketch": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, C.POINTER(TimelineParams), C.c_uint32, _VP]),
+    "isim_closed_loop_schedule": (C.c_int, [C.POINTER(ClosedLoop), C.c_uint64, C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint64)]),
+    "isim_closed_loop_host": (C.c_int, [C.POINTER(ClosedLoop), _VP, C.c_uint64, _VP, _VP, _VP]),
+    "isim_closed_loop_workspace_bytes": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "isim_closed_loop_device": (C.c_int, [C.POINTER(ClosedLoop), _VP, C.c_uint64, _VP, _VP, _VP, _VP, C.c_uint64,
+                                          _VP]),
+    "isim_closed_loop": (C.c_int, [C.c_int, C.POINTER(ClosedLoop), _VP, C.c_uint64, _VP, _VP, _VP]),
 }
 
 _lib = None
