@@ -61,6 +61,8 @@ struct DevState {
   uint32_t *d_dur = nullptr;   // dynamic walks: per-slot duration-table word (row | leaf bucket << 24)
   unsigned long long *d_work = nullptr;  // kWorkSlots sets of batch queues, zero between launches
   uint32_t *d_stage = nullptr;  // draw stream: kWorkSlots rows of n_slots u32 500 counts, zero between launches
+  isim::GroupEnt *d_gtab = nullptr;  // draw stream: kWorkSlots group tables, each written by its launch (or none)
+  uint32_t gtab_groups = 0;          // Philox groups of the stream (a table: + kGroupPad entries)
   // draw-free static walks (no error draw anywhere): every trace walks alike
   bool draw_free = false;
   uint64_t *d_const_stats = nullptr;     // the stats of one trace (computed on first use)
@@ -126,7 +128,7 @@ void free_des(DevState &d) {
 void free_dev(DevState &d) {
   free_des(d);
   for (void *q : {(void *)d.d_prog, (void *)d.d_mult, (void *)d.d_closes, (void *)d.d_close_end,
-                  (void *)d.d_close_slot, (void *)d.d_mark_end, (void *)d.d_mark_slot, (void *)d.d_dur, (void *)d.d_work, (void *)d.d_stage, (void *)d.d_const_stats,
+                  (void *)d.d_close_slot, (void *)d.d_mark_end, (void *)d.d_mark_slot, (void *)d.d_dur, (void *)d.d_work, (void *)d.d_stage, (void *)d.d_gtab, (void *)d.d_const_stats,
                   (void *)d.d_tree_ext, (void *)d.d_tree_dyn, (void *)d.d_tree_step,
                   (void *)d.d_sum_row, (void *)d.d_slot_tc, (void *)d.d_lds_slot})
     if (q) (void)hipFree(q);
@@ -448,6 +450,13 @@ int build_device(isim_handler *h, int device, DevState &st) {
       HIPCHK(hipMalloc(&st.d_stage, bytes));
       HIPCHK(hipMemset(st.d_stage, 0, bytes));
     }
+    // the launches' group tables, while kWorkSlots of them stay within the
+    // cap (ISIM_NO_GROUP_TABLE=1, for tests: none, as for a longer stream)
+    st.gtab_groups = (p.stream_nodes + 3) / 4;
+    const size_t tab_bytes = (size_t)(st.gtab_groups + isim::kGroupPad) * sizeof(isim::GroupEnt) * isim::kWorkSlots;
+    const char *no_tab = std::getenv("ISIM_NO_GROUP_TABLE");
+    if (tab_bytes <= isim::kGroupTableMaxBytes && !(no_tab && no_tab[0] == '1'))
+      HIPCHK(hipMalloc(&st.d_gtab, tab_bytes));
   }
   return ISIM_OK;
 }
@@ -705,6 +714,15 @@ static int launch_walk_one(isim_handler *h, DevState *st, uint64_t trace_begin, 
   kp.mark_words = st->mark_words;
   const void *prog = st->d_prog;
   const uint32_t *dur = st->d_dur;
+  if (st->d_gtab) {  // the launch's group table, for the trace ids' high word at its first trace
+    isim::GroupEnt *tab = st->d_gtab + (size_t)slot * (st->gtab_groups + isim::kGroupPad);
+    uint32_t n_groups = st->gtab_groups;
+    kp.gtab = tab;
+    kp.gtab_t_hi = (uint32_t)(trace_begin >> 32);
+    void *args0[] = {&prog, &n_groups, &kp.seed_lo, &kp.seed_hi, &kp.gtab_t_hi, &tab};
+    HIPCHK(hipLaunchKernel(isim::group_table_kernel(), dim3((n_groups + isim::kGroupPad + 255) / 256), dim3(256), args0,
+                           0, (hipStream_t)hip_stream));
+  }
   void *args[] = {&prog, &d_records, &d_stats, &dur, &kp};
   if (st->d_spill[0]) {
     // a spilling walk: the area its stream used last (else the next one,

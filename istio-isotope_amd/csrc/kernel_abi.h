@@ -211,6 +211,7 @@ struct TreeLayout {
 
 // Scalar kernel arguments (the program, records and stats pointers are
 // separate __restrict__ kernel arguments so program fetches become s_load).
+struct GroupEnt;  // below, with the work slots
 struct KParams {
   uint64_t trace_begin;
   uint64_t n_traces;
@@ -224,6 +225,8 @@ struct KParams {
   uint32_t root_dur;        // the entry's duration-table word (row | leaf bucket << 24)
   unsigned long long *work; // batch queues (kWorkWords): zero at launch, zeroed again by the last wave
   uint32_t *stage;          // draw stream: u32 per-site 500 counts of this launch (null: u64 atomics into stats)
+  const GroupEnt *gtab;     // draw stream: the launch's group table (null: scalar rounds in the kernel)
+  uint32_t gtab_t_hi;       // the high word of the trace ids the table was built for
   const StreamClose *closes;     // kind 6: close list (+kClosePad zero records of tail padding)
   const uint32_t *close_slot;    // kind 6: per close, the call-site slot of the closing invocation
   const uint32_t *close_end;     // kind 6: per chunk, closes up to and including it
@@ -257,6 +260,22 @@ constexpr uint32_t kWorkSlots = 256;
 // count at a site below 2^32); isim_stream_calls adds the row to the u64
 // stats and zeroes it.  Graphs with more slots keep the u64 atomics.
 constexpr uint32_t kStageMaxSlots = 1u << 16;
+// Draw-stream launches also fill a group table in their work slot
+// (isim_group_table, before the walk): per Philox group what every wave of the
+// launch would otherwise derive in scalar code, rounds 1-2 of the wave-uniform
+// counter words (a function of the group, the seed and the high word of the
+// trace ids) and the group's record tests.  n_groups + kGroupPad entries per
+// slot (zero tail padding, as the stream's).  Streams whose kWorkSlots tables
+// exceed kGroupTableMaxBytes get none and keep the in-kernel scalar rounds.
+struct GroupEnt {
+  uint32_t uk0, uk1, d;  // philox_lockstep's round-2 words of the group
+  uint32_t flags;        // kGroupAnyThr | kGroupAnyAlways
+};
+static_assert(sizeof(GroupEnt) == 16, "GroupEnt must be 16 bytes");
+constexpr uint32_t kGroupAnyThr = 1u;              // some record of the group has a non-zero threshold
+constexpr uint32_t kGroupAnyAlways = 0x80000000u;  // some record is an errorRate-1 record
+constexpr uint32_t kGroupPad = 2;
+constexpr uint64_t kGroupTableMaxBytes = 64ull << 20;
 
 constexpr uint32_t kWgThreads = 1024;                 // max workgroup size (launch bound)
 constexpr uint32_t kLdsAccBytes = 64;                 // WgAcc
@@ -291,6 +310,7 @@ inline void *tree_kernel(bool modeb, uint32_t frames, bool spill, bool nodes_lds
               : tree_kernel_m0c0(frames, spill, nodes_lds, draw, occ2, t64, wide, dag);
 }
 void *stream_calls_kernel();
+void *group_table_kernel();  // (stream, n_groups, seed_lo, seed_hi, t_hi, table): walk.hip isim_group_table
 void *mark_fold_kernel();  // kind 8: the per-launch fold of the position marks (walk.hip isim_mark_fold)
 void *fill_const_kernel();  // (records, n, record, one-trace stats, stats, stats words)
 uint32_t stream_traces_per_wave();

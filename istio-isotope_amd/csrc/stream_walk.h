@@ -9,7 +9,9 @@
 // the per-site error counters.  Four records share one Philox block and one
 // s_load_dwordx8, loaded one group ahead of the group being processed (the
 // device buffer carries two zero groups of tail padding, so the group loops
-// load past the last group without a bound test).
+// load past the last group without a bound test).  What a group's Philox
+// blocks need of the wave-uniform counter words comes from the launch's group
+// table (kernel_abi.h GroupEnt), loaded the same way, when the batch may use it.
 //
 // The five walkers differ in what a record's error mask is used for; they
 // share the batch setup (StreamBatch), the group's draws (stream_draws), the
@@ -42,6 +44,18 @@ __device__ __forceinline__ Node4 load_group(CNode4 *p) {
     r.n[j].thr = p->n[j].thr;
     r.n[j].meta = p->n[j].meta;
   }
+  return r;
+}
+
+// The launch's group table (kernel_abi.h GroupEnt), read like the stream: one
+// s_load_dwordx4 per group.
+typedef const __attribute__((address_space(4))) GroupEnt CEnt;
+__device__ __forceinline__ GroupEnt load_ent(CEnt *p) {
+  GroupEnt r;
+  r.uk0 = p->uk0;
+  r.uk1 = p->uk1;
+  r.d = p->d;
+  r.flags = p->flags;
   return r;
 }
 
@@ -104,21 +118,28 @@ struct StreamBatch {
   }
 };
 
-// TPL Philox blocks (one per trace of the lane) of counter (t_lo[u], t_hi, g, 0)
-// in lockstep: the round keys and the scalar rounds 1-2 (all counter words
-// but t_lo are wave-uniform) are shared by the TPL chains.
-template <int TPL>
-__device__ __forceinline__ void philox_lockstep(const uint32_t (&t_lo)[TPL], uint32_t t_hi_u, uint32_t g,
-                                                uint32_t k0a, uint32_t k1a, uint32_t (&x)[TPL][4]) {
+// Rounds 1-2 of the wave-uniform counter words (t_hi, g, 0) of a group's
+// Philox blocks: what the vector rounds need of them, as GroupEnt's words.
+// Shared by the walkers (scalar code, per wave and group) and the launch's
+// group table (isim_group_table, once per group).
+__host__ __device__ __forceinline__ void philox_uniform_rounds(uint32_t t_hi_u, uint32_t g, uint32_t k0a, uint32_t k1a,
+                                                               uint32_t &uk0, uint32_t &uk1, uint32_t &d) {
   const uint64_t q1 = (uint64_t)M1 * g;                      // scalar
   const uint32_t u0 = (uint32_t)(q1 >> 32) ^ t_hi_u ^ k0a;   // uniform
   const uint32_t u1 = (uint32_t)q1;                          // uniform
   const uint32_t k0b = k0a + W0, k1b = k1a + W1;
   const uint64_t q0 = (uint64_t)M0 * u0;                     // scalar (round 2)
-  // a VOP3 reads one SGPR: pre-xor the uniform words (opaque, so the
-  // compiler does not re-fold them into a two-SGPR v_bitop3 + v_mov)
-  uint32_t uk0 = u1 ^ k0b, uk1 = (uint32_t)(q0 >> 32) ^ k1b;
-  asm volatile("" : "+s"(uk0), "+s"(uk1));
+  uk0 = u1 ^ k0b;
+  uk1 = (uint32_t)(q0 >> 32) ^ k1b;
+  d = (uint32_t)q0;
+}
+
+// TPL Philox blocks (one per trace of the lane) of counter (t_lo[u], t_hi, g, 0)
+// in lockstep, given rounds 1-2 of the wave-uniform words (uk0, uk1, d): the
+// round keys are shared by the TPL chains.
+template <int TPL>
+__device__ __forceinline__ void philox_lockstep_from(const uint32_t (&t_lo)[TPL], uint32_t k0a, uint32_t k1a,
+                                                     uint32_t uk0, uint32_t uk1, uint32_t d0, uint32_t (&x)[TPL][4]) {
   uint32_t a[TPL], b[TPL], cc[TPL], d[TPL];
 #pragma unroll
   for (int u = 0; u < TPL; ++u) {
@@ -128,9 +149,9 @@ __device__ __forceinline__ void philox_lockstep(const uint32_t (&t_lo)[TPL], uin
     a[u] = (uint32_t)(p1 >> 32) ^ uk0;
     b[u] = (uint32_t)p1;
     cc[u] = (uint32_t)p0 ^ uk1;
-    d[u] = (uint32_t)q0;
+    d[u] = d0;
   }
-  uint32_t k0 = k0b + W0, k1 = k1b + W1;
+  uint32_t k0 = k0a + 2u * W0, k1 = k1a + 2u * W1;
 #pragma unroll
   for (int r = 2; r < 10; ++r) {
     // recompute the round keys per group (2 s_add) instead of letting the
@@ -149,6 +170,19 @@ __device__ __forceinline__ void philox_lockstep(const uint32_t (&t_lo)[TPL], uin
     x[u][2] = cc[u];
     x[u][3] = d[u];
   }
+}
+
+// ... with the scalar rounds 1-2 computed here (all counter words but t_lo
+// are wave-uniform): the batches without a group table.
+template <int TPL>
+__device__ __forceinline__ void philox_lockstep(const uint32_t (&t_lo)[TPL], uint32_t t_hi_u, uint32_t g,
+                                                uint32_t k0a, uint32_t k1a, uint32_t (&x)[TPL][4]) {
+  uint32_t uk0, uk1, d;
+  philox_uniform_rounds(t_hi_u, g, k0a, k1a, uk0, uk1, d);
+  // a VOP3 reads one SGPR: pre-xor the uniform words (opaque, so the
+  // compiler does not re-fold them into a two-SGPR v_bitop3 + v_mov)
+  asm volatile("" : "+s"(uk0), "+s"(uk1));
+  philox_lockstep_from<TPL>(t_lo, k0a, k1a, uk0, uk1, d, x);
 }
 
 __device__ __forceinline__ uint32_t thr_or(const Node4 &q) {
@@ -180,7 +214,33 @@ __device__ __forceinline__ void stream_draws(const Ctx &c, const StreamBatch<TPL
   }
 }
 
-// Groups [g0, g1) through grp(records, g), two per trip, each group's records
+// The same draws from the group's table entry (the batch is hi_uniform and
+// its t_hi is the table's): no scalar rounds, and the threshold test is a bit
+// of the entry.
+template <int TPL>
+__device__ __forceinline__ void stream_draws_tab(const Ctx &c, const StreamBatch<TPL> &bt, const GroupEnt &e,
+                                                 uint32_t (&x)[TPL][4]) {
+  if (e.flags & kGroupAnyThr) {
+    philox_lockstep_from<TPL>(bt.t_lo, c.k0, c.k1, e.uk0, e.uk1, e.d, x);
+  } else {
+    // the zeros stay in this (rare) branch: written before the test, as
+    // `x = 0; if (...) philox`, they were 4 TPL v_mov in every group
+    uint32_t z = 0;
+    asm volatile("" : "+v"(z));
+#pragma unroll
+    for (int u = 0; u < TPL; ++u) x[u][0] = x[u][1] = x[u][2] = x[u][3] = z;
+  }
+}
+
+// A batch draws from the launch's group table when there is one, the batch
+// does not straddle 2^32 and its t_hi is the one the table was built for (a
+// launch that crosses 2^32: the batches before the crossing).
+template <int TPL>
+__device__ __forceinline__ bool use_group_table(const StreamBatch<TPL> &bt, CEnt *tab, uint32_t tab_t_hi) {
+  return tab != nullptr && bt.hi_uniform && bt.t_hi_u == tab_t_hi;
+}
+
+// Groups [g0, g1) through grp(records, entry, g), two per trip, each group's records
 // loaded one group ahead into the other buffer; `cur` holds group g0 on entry
 // and group g1 on return.  No register copy between the buffers: with
 // `cur = nxt` the compiler waited for each prefetch right after issuing it,
@@ -188,37 +248,62 @@ __device__ __forceinline__ void stream_draws(const Ctx &c, const StreamBatch<TPL
 // other buffer has arrived (an empty asm reads it): scalar loads return out of
 // order, so a wait for that buffer placed after the load's issue would wait
 // for the load too.
-template <typename F>
-__device__ __forceinline__ void stream_pingpong(CNode4 *__restrict__ stream, Node4 &cur, uint32_t g0, uint32_t g1,
-                                                F &&grp) {
+// TAB: the groups' table entries travel with their records (a second
+// ping-pong buffer, ecur); else `tab` is not read and the entries are zero.
+template <bool TAB, typename F>
+__device__ __forceinline__ void stream_pingpong(CNode4 *__restrict__ stream, CEnt *__restrict__ tab, Node4 &cur,
+                                                GroupEnt &ecur, uint32_t g0, uint32_t g1, F &&grp) {
   uint32_t g = g0;
   for (; g + 1 < g1; g += 2) {
     CNode4 *pb = stream + g + 1;
-    asm volatile("" : "+s"(pb) : "s"(cur.n[0].thr));
+    GroupEnt eb{};
+    if constexpr (TAB) {
+      CEnt *qb = tab + g + 1;
+      asm volatile("" : "+s"(pb), "+s"(qb) : "s"(cur.n[0].thr), "s"(ecur.flags));
+      eb = load_ent(qb);
+    } else {
+      asm volatile("" : "+s"(pb) : "s"(cur.n[0].thr));
+    }
     const Node4 b = load_group(pb);
-    grp(cur, g);
+    grp(cur, ecur, g);
     CNode4 *pc = stream + g + 2;
-    asm volatile("" : "+s"(pc) : "s"(b.n[0].thr));
+    if constexpr (TAB) {
+      CEnt *qc = tab + g + 2;
+      asm volatile("" : "+s"(pc), "+s"(qc) : "s"(b.n[0].thr), "s"(eb.flags));
+      ecur = load_ent(qc);
+    } else {
+      asm volatile("" : "+s"(pc) : "s"(b.n[0].thr));
+    }
     cur = load_group(pc);
-    grp(b, g + 1);
+    grp(b, eb, g + 1);
   }
   if (g < g1) {
     const Node4 b = load_group(stream + g + 1);
-    grp(cur, g);
+    GroupEnt eb{};
+    if constexpr (TAB) eb = load_ent(tab + g + 1);
+    grp(cur, ecur, g);
     cur = b;
+    ecur = eb;
   }
 }
 
-// Every group of the stream through group(records, g): group g + 1 is loaded
-// before group g is processed and handed over by a loop-carried copy after
-// it, so the s_waitcnt for the load lands after a whole group of Philox work.
-template <typename F>
-__device__ __forceinline__ void stream_one_ahead(CNode4 *__restrict__ stream, uint32_t n_groups, F &&group) {
+// Every group of the stream through group(records, entry, g): group g + 1 is
+// loaded before group g is processed and handed over by a loop-carried copy
+// after it, so the s_waitcnt for the load lands after a whole group of Philox
+// work.
+template <bool TAB, typename F>
+__device__ __forceinline__ void stream_one_ahead(CNode4 *__restrict__ stream, CEnt *__restrict__ tab,
+                                                 uint32_t n_groups, F &&group) {
   Node4 cur = load_group(stream);
+  GroupEnt ecur{};
+  if constexpr (TAB) ecur = load_ent(tab);
   for (uint32_t g = 0; g < n_groups; ++g) {
     const Node4 nxt = load_group(stream + g + 1);
-    group(cur, g);
+    GroupEnt enxt{};
+    if constexpr (TAB) enxt = load_ent(tab + g + 1);
+    group(cur, ecur, g);
     cur = nxt;
+    ecur = enxt;
   }
 }
 
@@ -230,7 +315,8 @@ __device__ __forceinline__ void stream_one_ahead(CNode4 *__restrict__ stream, ui
 template <bool LDSC, int TPL, bool BS>
 __device__ __forceinline__ void walk_stream(const Ctx &c, CNode4 *__restrict__ stream, uint32_t n_groups,
                                             uint32_t n_nodes, uint64_t t_static, uint64_t trace_begin,
-                                            uint64_t n_traces, uint64_t base) {
+                                            uint64_t n_traces, uint64_t base, CEnt *__restrict__ tab,
+                                            uint32_t tab_t_hi) {
   const StreamBatch<TPL> bt(trace_begin, n_traces, base);
   const bool lane0 = lane_id() == 0;
   uint32_t errh[TPL];
@@ -381,18 +467,26 @@ __device__ __forceinline__ void walk_stream(const Ctx &c, CNode4 *__restrict__ s
       }
     }
   };
-  // record 0 (in group 0) is the entry invocation (the client request)
-  stream_one_ahead(stream, n_groups, [&](const Node4 &q, uint32_t g) {
-    uint32_t x[TPL][4];
-    stream_draws(c, bt, bt.hi_uniform, thr_or(q), g, x);
+  // record 0 (in group 0) is the entry invocation (the client request).
+  // T: the draws come from the group table (one instantiation of the loop
+  // each, so the test stays out of it)
+  auto groups = [&](auto T) {
+    constexpr bool TAB = decltype(T)::value;
+    stream_one_ahead<TAB>(stream, tab, n_groups, [&](const Node4 &q, const GroupEnt &e, uint32_t g) {
+      uint32_t x[TPL][4];
+      if constexpr (TAB) stream_draws_tab(c, bt, e, x);
+      else stream_draws(c, bt, bt.hi_uniform, thr_or(q), g, x);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      uint32_t xw[TPL];
+      for (int j = 0; j < 4; ++j) {
+        uint32_t xw[TPL];
 #pragma unroll
-      for (int u = 0; u < TPL; ++u) xw[u] = x[u][j];
-      node(q.n[j].thr, q.n[j].meta, xw);
-    }
-  });
+        for (int u = 0; u < TPL; ++u) xw[u] = x[u][j];
+        node(q.n[j].thr, q.n[j].meta, xw);
+      }
+    });
+  };
+  if (use_group_table(bt, tab, tab_t_hi)) groups(std::true_type{});
+  else groups(std::false_type{});
 #pragma unroll
   for (int u = 0; u < TPL; ++u) bt.finish(c, u, t_static, n_nodes, root_st[u], errh[u]);
 }
@@ -413,7 +507,8 @@ template <bool LDSC, int TPL, bool FULL>
 __device__ __forceinline__ void walk_stream_a(const Ctx &c, CNode4 *__restrict__ stream, uint32_t n_groups,
                                               uint32_t n_nodes, uint64_t t_static, uint64_t trace_begin,
                                               uint64_t n_traces, uint64_t base,
-                                              const uint32_t *__restrict__ stream_w) {
+                                              const uint32_t *__restrict__ stream_w, CEnt *__restrict__ tab,
+                                              uint32_t tab_t_hi) {
   const StreamBatch<TPL> bt(trace_begin, n_traces, base);
   static_assert(64 * TPL < 256, "a record's 500 count is packed into a byte");
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -431,9 +526,14 @@ __device__ __forceinline__ void walk_stream_a(const Ctx &c, CNode4 *__restrict__
     for (int u = 0; u < TPL; ++u)
       root_st[u] = (cur.n[0].meta & 0x80000000u) ? bt.all[u] : (ballot(x[u][0] < cur.n[0].thr) & bt.all[u]);
   }
-  // HU: the batch does not straddle 2^32 (one instantiation of the loop each,
-  // so the test stays out of it)
-  auto chunks = [&](auto HU) {
+  // DR: where the groups' draws come from (one instantiation of the loop
+  // each, so the test stays out of it): 2 the launch's group table, 1 lockstep
+  // blocks with the scalar rounds here (the batch does not straddle 2^32),
+  // 0 a block per trace
+  auto chunks = [&](auto DR) {
+    constexpr bool TAB = decltype(DR)::value == 2;
+    GroupEnt ecur{};
+    if constexpr (TAB) ecur = load_ent(tab);
     for (uint32_t g0 = 0; g0 < n_groups; g0 += kCountGroups) {
       const uint32_t ng = n_groups - g0 < kCountGroups ? n_groups - g0 : kCountGroups;
       // this lane's group of the chunk (thr, meta of its four records)
@@ -446,12 +546,19 @@ __device__ __forceinline__ void walk_stream_a(const Ctx &c, CNode4 *__restrict__
       uint32_t pk = 0;  // lane l: the 500 counts of group g0 + l, a byte per record
       // one group: its Philox blocks, per record and trace the compare and the
       // carried add, the four counts into the group's lane of pk
-      stream_pingpong(stream, cur, g0, g0 + ng, [&](const Node4 &q, uint32_t g) {
+      stream_pingpong<TAB>(stream, tab, cur, ecur, g0, g0 + ng, [&](const Node4 &q, const GroupEnt &e, uint32_t g) {
         uint32_t x[TPL][4];
-        uint64_t qor = 0;  // s_or_b64: both tests of the group from three scalar ORs of its (thr, meta) pairs
+        bool any_always;  // the group holds an errorRate-1 record
+        if constexpr (TAB) {
+          stream_draws_tab(c, bt, e, x);
+          any_always = (int32_t)e.flags < 0;  // kGroupAnyAlways
+        } else {
+          uint64_t qor = 0;  // s_or_b64: both tests of the group from three scalar ORs of its (thr, meta) pairs
 #pragma unroll
-        for (int j = 0; j < 4; ++j) qor |= u64of(q.n[j].thr, q.n[j].meta);
-        stream_draws(c, bt, decltype(HU)::value, (uint32_t)qor, g, x);
+          for (int j = 0; j < 4; ++j) qor |= u64of(q.n[j].thr, q.n[j].meta);
+          stream_draws(c, bt, decltype(DR)::value == 1, (uint32_t)qor, g, x);
+          any_always = (int64_t)qor < 0;
+        }
         uint64_t own[TPL][4];
         uint32_t w = 0;
 #pragma unroll
@@ -469,7 +576,7 @@ __device__ __forceinline__ void walk_stream_a(const Ctx &c, CNode4 *__restrict__
         // errorRate-1 records (always 500, thr 0: no lane counted above) are
         // rare: one test per group, a test per record only in the groups
         // that hold one
-        if ((int64_t)qor < 0) {
+        if (any_always) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             if (!(q.n[j].meta & 0x80000000u)) continue;
@@ -493,8 +600,9 @@ __device__ __forceinline__ void walk_stream_a(const Ctx &c, CNode4 *__restrict__
       }
     }
   };
-  if (bt.hi_uniform) chunks(std::true_type{});
-  else chunks(std::false_type{});
+  if (use_group_table(bt, tab, tab_t_hi)) chunks(std::integral_constant<int, 2>{});
+  else if (bt.hi_uniform) chunks(std::integral_constant<int, 1>{});
+  else chunks(std::integral_constant<int, 0>{});
 #pragma unroll
   for (int u = 0; u < TPL; ++u) bt.finish(c, u, t_static, n_nodes, root_st[u], errh[u]);
 }
@@ -531,7 +639,8 @@ __device__ __forceinline__ void walk_stream_cl(const Ctx &c, CNode4 *__restrict_
                                                uint32_t n_nodes, uint64_t t_static, uint64_t trace_begin,
                                                uint64_t n_traces, uint64_t base, CClose *__restrict__ closes,
                                                const uint32_t *__restrict__ close_slot, CU32 *__restrict__ close_end,
-                                               const uint32_t *__restrict__ stream_w) {
+                                               const uint32_t *__restrict__ stream_w, CEnt *__restrict__ tab,
+                                               uint32_t tab_t_hi) {
   const StreamBatch<TPL> bt(trace_begin, n_traces, base);
   const uint32_t lane = lane_id();
   uint32_t errh[TPL], le[TPL];
@@ -539,6 +648,9 @@ __device__ __forceinline__ void walk_stream_cl(const Ctx &c, CNode4 *__restrict_
   for (int u = 0; u < TPL; ++u) errh[u] = le[u] = 0;
 
   Node4 cur = load_group(stream);
+  const bool use_tab = use_group_table(bt, tab, tab_t_hi);
+  GroupEnt ecur{};
+  if (use_tab) ecur = load_ent(tab);
   uint32_t cp = 0;
   const uint32_t n_chunks = (n_groups + kChunkGroups - 1) / kChunkGroups;
   for (uint32_t ch = 0; ch < n_chunks; ++ch) {
@@ -554,30 +666,41 @@ __device__ __forceinline__ void walk_stream_cl(const Ctx &c, CNode4 *__restrict_
     for (int u = 0; u < TPL; ++u) mb[u] = 0;
     // one group: its Philox blocks, then per record the error bits shifted
     // into mb and the record's count in lane r of lcnt
-    stream_pingpong(stream, cur, g0, g1, [&](const Node4 &q, uint32_t g) {
-      uint32_t x[TPL][4];
-      stream_draws(c, bt, bt.hi_uniform, thr_or(q), g, x);
-      auto records = [&](bool always) {
+    // T: the draws come from the group table (chosen per chunk, outside the
+    // group loop)
+    auto groups = [&](auto T) {
+      constexpr bool TAB = decltype(T)::value;
+      stream_pingpong<TAB>(stream, tab, cur, ecur, g0, g1, [&](const Node4 &q, const GroupEnt &e, uint32_t g) {
+        uint32_t x[TPL][4];
+        if constexpr (TAB) stream_draws_tab(c, bt, e, x);
+        else stream_draws(c, bt, bt.hi_uniform, thr_or(q), g, x);
+        auto records = [&](bool always) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint32_t thr = q.n[j].thr, meta = q.n[j].meta;
-          uint32_t n = 0;
+          for (int j = 0; j < 4; ++j) {
+            const uint32_t thr = q.n[j].thr, meta = q.n[j].meta;
+            uint32_t n = 0;
 #pragma unroll
-          for (int u = 0; u < TPL; ++u) {
-            uint64_t own = ballot(x[u][j] < thr);
-            if (always && (meta & 0x80000000u)) own = ~0ull;
-            shift_in(mb[u], own);
-            if constexpr (!FULL) own &= bt.all[u];
-            n += popc(own);
+            for (int u = 0; u < TPL; ++u) {
+              uint64_t own = ballot(x[u][j] < thr);
+              if (always && (meta & 0x80000000u)) own = ~0ull;
+              shift_in(mb[u], own);
+              if constexpr (!FULL) own &= bt.all[u];
+              n += popc(own);
+            }
+            lcnt = wrl(n, 4u * (g - g0) + j, lcnt);  // lane r: record r's count
           }
-          lcnt = wrl(n, 4u * (g - g0) + j, lcnt);  // lane r: record r's count
-        }
-      };
-      // errorRate-1 records (always 500) are rare: a branch per record only
-      // in the groups that hold one
-      if (((q.n[0].meta | q.n[1].meta | q.n[2].meta | q.n[3].meta) & 0x80000000u) == 0) records(false);
-      else records(true);
-    });
+        };
+        // errorRate-1 records (always 500) are rare: a branch per record only
+        // in the groups that hold one
+        bool any_always;
+        if constexpr (TAB) any_always = (e.flags & kGroupAnyAlways) != 0;
+        else any_always = ((q.n[0].meta | q.n[1].meta | q.n[2].meta | q.n[3].meta) & 0x80000000u) != 0;
+        if (!any_always) records(false);
+        else records(true);
+      });
+    };
+    if (use_tab) groups(std::true_type{});
+    else groups(std::false_type{});
     // leaves respond with their own draw: their error counts (lane r =
     // record r) go to the site table in one ds_add, their 500s to errh
     {
@@ -644,7 +767,8 @@ __device__ __forceinline__ void walk_stream_cl(const Ctx &c, CNode4 *__restrict_
 template <int TPL, bool FULL>
 __device__ __forceinline__ void walk_stream_mark(const Ctx &c, CNode4 *__restrict__ stream, uint32_t n_groups,
                                                  uint32_t n_nodes, uint64_t t_static, uint64_t trace_begin,
-                                                 uint64_t n_traces, uint64_t base) {
+                                                 uint64_t n_traces, uint64_t base, CEnt *__restrict__ tab,
+                                                 uint32_t tab_t_hi) {
   const StreamBatch<TPL> bt(trace_begin, n_traces, base);
   const bool lane0 = lane_id() == 0;
   uint32_t errh[TPL], mk[TPL];
@@ -654,39 +778,47 @@ __device__ __forceinline__ void walk_stream_mark(const Ctx &c, CNode4 *__restric
     mk[u] = 0xFFFFFFFFu;
   }
   uint32_t *marks = c.cnt;
-  stream_one_ahead(stream, n_groups, [&](const Node4 &q, uint32_t g) {
-    uint32_t x[TPL][4];
-    stream_draws(c, bt, bt.hi_uniform, thr_or(q), g, x);
+  // T: the draws come from the group table (one instantiation of the loop
+  // each, so the test stays out of it)
+  auto groups = [&](auto T) {
+    constexpr bool TAB = decltype(T)::value;
+    stream_one_ahead<TAB>(stream, tab, n_groups, [&](const Node4 &q, const GroupEnt &e, uint32_t g) {
+      uint32_t x[TPL][4];
+      if constexpr (TAB) stream_draws_tab(c, bt, e, x);
+      else stream_draws(c, bt, bt.hi_uniform, thr_or(q), g, x);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t kw = q.n[j].meta;
-      const uint32_t key = kw & kMarkKeyMask;
-      const uint64_t always = (kw & 0x80000000u) ? ~0ull : 0ull;  // errorRate 1: no draw, always 500
-      uint64_t own[TPL], any = 0;
-#pragma unroll
-      for (int u = 0; u < TPL; ++u) {
-        own[u] = ballot(x[u][j] < q.n[j].thr) | always;
-        if constexpr (!FULL) own[u] &= bt.all[u];
-        mk[u] = mk[u] < key ? mk[u] : key;
-        any |= own[u];
-      }
-      if (any) {
-        uint32_t n = 0;
-#pragma unroll
-        for (int u = 0; u < TPL; ++u) n += popc(own[u]);
-        if (lane0) atomicAdd(marks + 4u * g + (uint32_t)j, n);
-        const uint32_t d1 = (key >> 24) + 1u;
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t kw = q.n[j].meta;
+        const uint32_t key = kw & kMarkKeyMask;
+        const uint64_t always = (kw & 0x80000000u) ? ~0ull : 0ull;  // errorRate 1: no draw, always 500
+        uint64_t own[TPL], any = 0;
 #pragma unroll
         for (int u = 0; u < TPL; ++u) {
-          if (lane_in(own[u])) {
-            atomicSub(marks + (mk[u] & kMarkPosMask), 1u);
-            errh[u] += d1 - (mk[u] >> 24);
-            mk[u] = 0xFFFFFFFFu;
+          own[u] = ballot(x[u][j] < q.n[j].thr) | always;
+          if constexpr (!FULL) own[u] &= bt.all[u];
+          mk[u] = mk[u] < key ? mk[u] : key;
+          any |= own[u];
+        }
+        if (any) {
+          uint32_t n = 0;
+#pragma unroll
+          for (int u = 0; u < TPL; ++u) n += popc(own[u]);
+          if (lane0) atomicAdd(marks + 4u * g + (uint32_t)j, n);
+          const uint32_t d1 = (key >> 24) + 1u;
+#pragma unroll
+          for (int u = 0; u < TPL; ++u) {
+            if (lane_in(own[u])) {
+              atomicSub(marks + (mk[u] & kMarkPosMask), 1u);
+              errh[u] += d1 - (mk[u] >> 24);
+              mk[u] = 0xFFFFFFFFu;
+            }
           }
         }
       }
-    }
-  });
+    });
+  };
+  if (use_group_table(bt, tab, tab_t_hi)) groups(std::true_type{});
+  else groups(std::false_type{});
 #pragma unroll
   for (int u = 0; u < TPL; ++u) bt.finish(c, u, t_static, n_nodes, ballot(errh[u] != 0u) & bt.all[u], errh[u]);
 }

@@ -501,6 +501,27 @@ __global__ void isim_stream_calls(const uint32_t *__restrict__ mult, uint32_t n_
   }
 }
 
+// The group table of one draw-stream launch (kernel_abi.h GroupEnt), launched
+// before the walk on the same stream: entry g holds rounds 1-2 of the
+// wave-uniform counter words of group g's Philox blocks, for trace ids with
+// high word t_hi, and the group's record tests; kGroupPad zero entries follow.
+__global__ void isim_group_table(const Node *__restrict__ stream, uint32_t n_groups, uint32_t seed_lo,
+                                 uint32_t seed_hi, uint32_t t_hi, GroupEnt *__restrict__ tab) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_groups + kGroupPad) return;
+  GroupEnt e{0u, 0u, 0u, 0u};
+  if (g < n_groups) {
+    philox_uniform_rounds(t_hi, g, seed_lo, seed_hi, e.uk0, e.uk1, e.d);
+    uint32_t thr = 0, meta = 0;
+    for (uint32_t j = 0; j < 4; ++j) {
+      thr |= stream[4u * g + j].thr;
+      meta |= stream[4u * g + j].meta;
+    }
+    e.flags = (thr ? kGroupAnyThr : 0u) | (meta & kGroupAnyAlways);
+  }
+  tab[g] = e;
+}
+
 // KIND: 0 static/u32 time, 1 static/u64, 2 dynamic/u32, 3 dynamic/u64, 4 draw stream
 // (mode B: the wave-mask stack), 5 draw stream with the mode-B bit stack (call
 // depth <= 32), 6 draw stream with the mode-B close list, 8 draw stream with
@@ -564,31 +585,36 @@ __global__ void __launch_bounds__(kWgThreads, KIND >= 4 ? ISIM_STREAM_WAVES : 1)
       const uint64_t base = b * kBatch;
       CNode4 *st = (CNode4 *)(const __attribute__((address_space(1))) Ins *)prog;
       const uint32_t ng = kp.n_nodes ? (kp.n_nodes + 3) / 4 : 0;
+      CEnt *gt = (CEnt *)(const __attribute__((address_space(1))) GroupEnt *)kp.gtab;
+      const uint32_t gth = kp.gtab_t_hi;
       // FULL (every lane of every trace slot valid) stays a plain if/else per
       // kind: behind a generic-lambda helper the same walkers were scheduled
       // differently and mode A measured 0.5 % slower
       if constexpr (KIND == 8) {
         if (base + 64 * kStreamTPL <= kp.n_traces)
-          walk_stream_mark<kStreamTPL, true>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base);
+          walk_stream_mark<kStreamTPL, true>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base, gt,
+                                             gth);
         else
-          walk_stream_mark<kStreamTPL, false>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base);
+          walk_stream_mark<kStreamTPL, false>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base, gt,
+                                              gth);
       } else if constexpr (KIND == 6) {
         CClose *cl = (CClose *)(const __attribute__((address_space(1))) StreamClose *)kp.closes;
         CU32 *ce = (CU32 *)(const __attribute__((address_space(1))) uint32_t *)kp.close_end;
         if (base + 64 * kStreamTPL <= kp.n_traces)
           walk_stream_cl<LDSC, kStreamTPL, true>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces,
-                                                 base, cl, kp.close_slot, ce, (const uint32_t *)prog);
+                                                 base, cl, kp.close_slot, ce, (const uint32_t *)prog, gt, gth);
         else
           walk_stream_cl<LDSC, kStreamTPL, false>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces,
-                                                  base, cl, kp.close_slot, ce, (const uint32_t *)prog);
+                                                  base, cl, kp.close_slot, ce, (const uint32_t *)prog, gt, gth);
       } else if constexpr (MODEB) {
-        walk_stream<LDSC, kStreamTPL, KIND == 5>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base);
+        walk_stream<LDSC, kStreamTPL, KIND == 5>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base,
+                                                 gt, gth);
       } else if (base + 64 * kStreamTPL <= kp.n_traces)  // every lane of every trace slot valid
         walk_stream_a<LDSC, kStreamTPL, true>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base,
-                                              (const uint32_t *)prog);
+                                              (const uint32_t *)prog, gt, gth);
       else
         walk_stream_a<LDSC, kStreamTPL, false>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base,
-                                               (const uint32_t *)prog);
+                                               (const uint32_t *)prog, gt, gth);
     }
     else if constexpr (STATIC) walk_static<MODEB, TT>(c, kp.trace_begin, kp.n_traces, b * 64);
     else walk_dynamic<MODEB, TT>(c, kp.trace_begin, kp.n_traces, b * 64, lstk, hstk);
@@ -657,6 +683,7 @@ void *walk_kernel(int kind, bool modeb, bool lds_counters) {
 void *mark_fold_kernel() { return (void *)&dev::isim_mark_fold; }
 
 void *stream_calls_kernel() { return (void *)&dev::isim_stream_calls; }
+void *group_table_kernel() { return (void *)&dev::isim_group_table; }
 void *fill_const_kernel() { return (void *)&dev::isim_fill_const; }
 uint32_t stream_traces_per_wave() { return 64u * (uint32_t)dev::kStreamTPL; }
 
