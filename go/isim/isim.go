@@ -255,6 +255,57 @@ func (c ClosedLoop) ArrivalsHost(recs []TraceRecord, firstIndex uint64, freeAt [
 	})
 }
 
+// Span is one executed invocation of a trace (isim_span, DESIGN §19): the call
+// occupies [StartNs, StartNs + HopNs + DurationNs] of the trace's time.
+type Span = C.isim_span
+
+// TraceSpans walks the listed traces again on GPU `device` and returns, per
+// trace, its executed invocations in hop order with their start times
+// (isim_trace_spans).  The handler must run a dynamic walk over an unrolled
+// tree (or be created with ISIM_FLAG_DYNAMIC).
+func (h *Handler) TraceSpans(device int, ids []uint64) ([][]Span, error) {
+	off := make([]uint64, len(ids)+1)
+	info := make([]uint64, C.ISIM_SPAN_INFO_WORDS)
+	// no room first: the call then only counts, and info tells the room the traces need
+	rc := C.isim_trace_spans(C.int(device), h.h, u64ptr(ids), C.uint64_t(len(ids)), u64ptr(off), nil, 0, u64ptr(info))
+	if err := lastErr(rc); err != nil {
+		return nil, err
+	}
+	spans := make([]Span, info[C.ISIM_SPAN_TOTAL]+1)
+	rc = C.isim_trace_spans(C.int(device), h.h, u64ptr(ids), C.uint64_t(len(ids)), u64ptr(off), &spans[0],
+		C.uint64_t(info[C.ISIM_SPAN_TOTAL]), u64ptr(info))
+	if err := lastErr(rc); err != nil {
+		return nil, err
+	}
+	out := make([][]Span, len(ids))
+	for i := range ids {
+		out[i] = spans[off[i]:off[i+1]]
+	}
+	return out, nil
+}
+
+// SelectTraces returns the ids begin + i of the records with a latency of at
+// least minLatencyNs in class cls (C.ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500), in
+// ascending i, at most maxIDs of them, and the number of matching records
+// (isim_select_traces, on GPU `device`).
+func SelectTraces(device int, recs []TraceRecord, begin, minLatencyNs uint64, cls uint32, maxIDs int) ([]uint64, uint64, error) {
+	var rp *TraceRecord
+	if len(recs) > 0 {
+		rp = &recs[0]
+	}
+	if maxIDs > len(recs) {
+		maxIDs = len(recs)
+	}
+	ids := make([]uint64, maxIDs)
+	info := make([]uint64, 2)
+	rc := C.isim_select_traces(C.int(device), rp, C.uint64_t(len(recs)), C.uint64_t(begin), C.uint64_t(minLatencyNs),
+		C.uint32_t(cls), C.uint64_t(maxIDs), u64ptr(ids), u64ptr(info))
+	if err := lastErr(rc); err != nil {
+		return nil, 0, err
+	}
+	return ids[:info[1]], info[0], nil
+}
+
 // TimelineRow is one row of a timeline table: the requests that arrived in
 // the window and, of those that completed in it, by code (0: 200, 1: 500),
 // their count, latency sum, latency maximum and Prometheus histogram.

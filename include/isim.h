@@ -826,6 +826,88 @@ ISIM_API int isim_closed_loop_device(const struct isim_closed_loop *cl, const is
 ISIM_API int isim_closed_loop(int device, const struct isim_closed_loop *cl, const isim_trace_rec *h_records, uint64_t n,
                               uint64_t *h_free_at, uint64_t *h_arrivals, uint64_t *h_info);
 
+/* ---- trace spans: the executed invocations of chosen traces (EXT) ----
+ * A dynamic walk keeps 16 bytes per trace.  A trace is a pure function of
+ * (seed, trace id), so the invocations behind any record come from walking
+ * that id again: the role of the reference's Jaeger spans (service/main.go).
+ * Handlers with an unrolled tree of potential invocations only (a dynamic walk,
+ * or any graph under ISIM_FLAG_DYNAMIC; not the site graph).
+ *
+ * The spans of one trace are contiguous and ordered by hop.  The entry's
+ * duration_ns is the record's latency_ns, its status bit 0 the record's status,
+ * the number of spans the record's hops, the spans with bit 0 set the record's
+ * 500 count.
+ *
+ * start_ns replays the caller's script (handler.go:66-76) with a
+ * clock that starts at the caller's own start_ns: a sleep adds max(d, 0); an
+ * executed call starts at the clock and adds H + T, a skipped call adds 0; every
+ * child of a concurrent step starts at the step's start, and the step adds the
+ * largest of its children's H + T and its sleeps. */
+typedef struct {
+  uint64_t start_ns;     /* when the caller sends the request, from the trace's start; entry 0 */
+  uint64_t duration_ns;  /* the callee's own duration T (§2.4): receipt to respond point, no hop cost */
+  uint64_t hop_ns;       /* H of the call site (§2.2); entry 0.  The call occupies [start, start + H + T] */
+  uint32_t hop;          /* preorder index among the trace's executed invocations (§2.3), entry 0 */
+  uint32_t caller_hop;   /* 0xFFFFFFFF for the entry */
+  uint32_t position;     /* position in the unrolled tree */
+  uint32_t slot;         /* call-site slot (isim_handler_slots); 0xFFFFFFFF for the entry */
+  uint32_t service;      /* callee service index; the entry service for hop 0 */
+  uint32_t status;       /* bit 0: responded 500; bit 1: its own error draw (mode B: bit 0 without bit 1 = a failed step) */
+} isim_span;             /* 48 bytes */
+
+#define ISIM_SPAN_TOTAL   0   /* spans of every listed trace (what cap_spans must reach for all to fit) */
+#define ISIM_SPAN_WRITTEN 1   /* traces written: the list entries before the first that did not fit */
+#define ISIM_SPAN_N_IDS   2   /* n_ids */
+#define ISIM_SPAN_FIRST_UNFIT 3 /* first list index whose spans did not fit cap_spans, or n_ids */
+#define ISIM_SPAN_INFO_WORDS 4
+
+/* host only, no GPU */
+ISIM_API int isim_trace_spans_workspace_bytes(const isim_handler *h, uint64_t n_ids, uint64_t *bytes);
+/* The spans of the traces d_trace_ids[0 .. n_ids) (any u64, unsorted, repeats
+ * allowed; n_ids <= 2^32) on the current device, asynchronously on hip_stream:
+ * d_off[n_ids + 1] the exclusive scan of the traces' hops, the spans of list
+ * entry i at d_spans[d_off[i] + hop] when d_off[i + 1] <= cap_spans (a trace
+ * that does not fit writes nothing), d_info[ISIM_SPAN_INFO_WORDS] written.
+ * start_ns is left 0 (isim_trace_spans_place fills it on the host).  Three
+ * steps ordered by the stream: a counting walk, a scan, an emitting walk.  No
+ * host synchronisation, graph-capturable from the first call, the workspace may
+ * be dirty (calls that share one must be ordered); the first call of a handler
+ * on a device uploads the handler's tree tables.  n_ids 0 writes d_off[0] = 0
+ * and d_info, nothing else.  ISIM_EINVAL, before any HIP call: a null argument,
+ * a handler without an unrolled tree (a static walk: create the handler with
+ * ISIM_FLAG_DYNAMIC) or on the site graph, n_ids above 2^32, buffers not 8-byte
+ * aligned, a workspace below isim_trace_spans_workspace_bytes(h, n_ids). */
+ISIM_API int isim_trace_spans_device(const isim_handler *h, const uint64_t *d_trace_ids, uint64_t n_ids,
+                                     uint64_t *d_off, isim_span *d_spans, uint64_t cap_spans, uint64_t *d_info,
+                                     void *d_workspace, uint64_t workspace_bytes, void *hip_stream);
+/* Synchronous convenience: host buffers, start_ns filled. */
+ISIM_API int isim_trace_spans(int device, const isim_handler *h, const uint64_t *h_trace_ids, uint64_t n_ids,
+                              uint64_t *h_off, isim_span *h_spans, uint64_t cap_spans, uint64_t *h_info);
+/* host only, no GPU: the same walk on the CPU, start_ns filled */
+ISIM_API int isim_trace_spans_host(const isim_handler *h, const uint64_t *h_trace_ids, uint64_t n_ids,
+                                   uint64_t *h_off, isim_span *h_spans, uint64_t cap_spans, uint64_t *h_info);
+/* host only, no GPU: fills start_ns of the n_written traces whose spans lie at
+ * h_spans[h_off[i] .. h_off[i + 1]), one pass per trace in hop order */
+ISIM_API int isim_trace_spans_place(const isim_handler *h, const uint64_t *h_off, uint64_t n_written,
+                                    isim_span *h_spans);
+
+/* The ids trace_begin + i, in ascending i, of the records with
+ * latency_ns >= min_latency_ns in class cls (ISIM_Q_ALL / ISIM_Q_200 /
+ * ISIM_Q_500): the first max_ids of them at d_ids, d_info = {matches, written}.
+ * Count per block, scan, scatter: the order is deterministic.  The contract of
+ * isim_trace_spans_device; n <= 2^40, records 16-byte aligned. */
+ISIM_API int isim_select_traces_workspace_bytes(uint64_t n, uint64_t *bytes);  /* host only */
+ISIM_API int isim_select_traces_device(const isim_trace_rec *d_records, uint64_t n, uint64_t trace_begin,
+                                       uint64_t min_latency_ns, uint32_t cls, uint64_t max_ids, uint64_t *d_ids,
+                                       uint64_t *d_info, void *d_workspace, uint64_t workspace_bytes,
+                                       void *hip_stream);
+ISIM_API int isim_select_traces(int device, const isim_trace_rec *h_records, uint64_t n, uint64_t trace_begin,
+                                uint64_t min_latency_ns, uint32_t cls, uint64_t max_ids, uint64_t *h_ids,
+                                uint64_t *h_info);
+ISIM_API int isim_select_traces_host(const isim_trace_rec *h_records, uint64_t n, uint64_t trace_begin,
+                                     uint64_t min_latency_ns, uint32_t cls, uint64_t max_ids, uint64_t *h_ids,
+                                     uint64_t *h_info);  /* no GPU */
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@
 #include "kernel_abi.h"
 #include "load_profile.h"
 #include "program.h"
+#include "spans.h"
 
 namespace {
 
@@ -161,6 +162,8 @@ struct isim_handler {
   isim::DesPlan des;
   std::mutex report_mu;
   isim::DesItemsReport des_report{};  // the item engine's last batch (isim_des_last_batch)
+  std::mutex span_mu;
+  std::shared_ptr<void> span_state;   // trace spans: the per-device tables of spans.hip (its own deleter)
   ~isim_handler() {
     for (auto &kv : dev) {
       int cur = 0;
@@ -171,6 +174,12 @@ struct isim_handler {
     }
   }
 };
+
+// what spans.cpp and spans.hip read of a handler (spans.h)
+isim::spans::HandlerView isim::spans::handler_view(const isim_handler *h) {
+  isim_handler *m = const_cast<isim_handler *>(h);
+  return HandlerView{&h->prog, &h->graph, &h->params, &m->span_mu, &m->span_state};
+}
 
 namespace {
 

@@ -68,6 +68,10 @@ CL_MAX_CONNECTIONS = 65536
 CL_UNIFORM = 1
 CL_MAKESPAN, CL_MIN_FREE, CL_LATE, CL_SUM_LATE = 0, 1, 2, 3
 CL_INFO_WORDS = 4
+# isim_trace_spans*: info words
+SPAN_TOTAL, SPAN_WRITTEN, SPAN_N_IDS, SPAN_FIRST_UNFIT = 0, 1, 2, 3
+SPAN_INFO_WORDS = 4
+SPAN_NONE = 0xFFFFFFFF  # the entry's caller_hop and slot
 
 
 def SK_BINS(s: int) -> int:
@@ -247,6 +251,17 @@ SIGNATURES = {
     "isim_closed_loop_device": (C.c_int, [C.POINTER(ClosedLoop), _VP, C.c_uint64, _VP, _VP, _VP, _VP, C.c_uint64,
                                           _VP]),
     "isim_closed_loop": (C.c_int, [C.c_int, C.POINTER(ClosedLoop), _VP, C.c_uint64, _VP, _VP, _VP]),
+    "isim_trace_spans_workspace_bytes": (C.c_int, [_VP, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "isim_trace_spans_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP]),
+    "isim_trace_spans": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP]),
+    "isim_trace_spans_host": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP]),
+    "isim_trace_spans_place": (C.c_int, [_VP, _VP, C.c_uint64, _VP]),
+    "isim_select_traces_workspace_bytes": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "isim_select_traces_device": (C.c_int, [_VP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, _VP,
+                                            _VP, _VP, C.c_uint64, _VP]),
+    "isim_select_traces": (C.c_int, [C.c_int, _VP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, _VP,
+                                     _VP]),
+    "isim_select_traces_host": (C.c_int, [_VP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, _VP, _VP]),
 }
 
 _lib = None
