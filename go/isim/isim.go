@@ -284,6 +284,56 @@ func (h *Handler) TraceSpans(device int, ids []uint64) ([][]Span, error) {
 	return out, nil
 }
 
+// The critical-path table (DESIGN §20): (services + 1) rows of CpRowWords
+// words, every word a sum mod 2^64 (tables merge by addition).  Row s holds
+// the Cp* words of service s, the last row the CpH* words.  SpanCritical is
+// the status bit of a span on the path.
+const (
+	SpanCritical  = C.ISIM_SPAN_CRITICAL
+	CpInvocations = C.ISIM_CP_INVOCATIONS
+	CpSumDuration = C.ISIM_CP_SUM_DURATION
+	CpCritical    = C.ISIM_CP_CRITICAL
+	CpSelfNs      = C.ISIM_CP_SELF_NS
+	CpHopNs       = C.ISIM_CP_HOP_NS
+	CpCritical500 = C.ISIM_CP_CRITICAL_500
+	CpRowWords    = C.ISIM_CP_ROW_WORDS
+	CpHTraces     = C.ISIM_CP_H_TRACES
+	CpHSpans      = C.ISIM_CP_H_SPANS
+	CpHCritical   = C.ISIM_CP_H_CRITICAL
+	CpHSumLatency = C.ISIM_CP_H_SUM_LATENCY
+	CpHRefused    = C.ISIM_CP_H_REFUSED
+)
+
+// CriticalPath walks the listed traces again on GPU `device`, marks the spans
+// on each trace's critical path (SpanCritical in Span.status) and returns them
+// with the table of per-service time on the path (isim_trace_spans, then
+// isim_critical_path).  Tables of several calls add word by word.
+func (h *Handler) CriticalPath(device int, ids []uint64) ([][]Span, []uint64, error) {
+	var words C.uint64_t
+	if err := lastErr(C.isim_critical_path_table_words(h.h, &words)); err != nil {
+		return nil, nil, err
+	}
+	traces, err := h.TraceSpans(device, ids)
+	if err != nil {
+		return nil, nil, err
+	}
+	// TraceSpans returns slices of one array, in list order: the offsets are their running lengths
+	off := make([]uint64, len(ids)+1)
+	for i, t := range traces {
+		off[i+1] = off[i] + uint64(len(t))
+	}
+	table := make([]uint64, words)
+	var first *Span
+	if len(traces) > 0 {
+		first = &traces[0][0] // every trace has its entry span
+	}
+	rc := C.isim_critical_path(C.int(device), h.h, u64ptr(off), C.uint64_t(len(ids)), first, u64ptr(table))
+	if err := lastErr(rc); err != nil {
+		return nil, nil, err
+	}
+	return traces, table, nil
+}
+
 // SelectTraces returns the ids begin + i of the records with a latency of at
 // least minLatencyNs in class cls (C.ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500), in
 // ascending i, at most maxIDs of them, and the number of matching records

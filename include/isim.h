@@ -908,6 +908,92 @@ ISIM_API int isim_select_traces_host(const isim_trace_rec *h_records, uint64_t n
                                      uint64_t min_latency_ns, uint32_t cls, uint64_t max_ids, uint64_t *h_ids,
                                      uint64_t *h_info);  /* no GPU */
 
+/* ---- critical path of chosen traces: per-service time on it (EXT) ----
+ * Across a list of traces (the tail of a batch, usually): which services hold
+ * the latency?  The rule, over one trace's spans in hop order and the handler's
+ * scripts.  Each caller's script is replayed as start_ns replays it (above):
+ * the clock starts at the caller's start_ns, the caller's executed children are
+ * taken in hop order, each matched to the call command whose index its
+ * position's node carries.
+ *
+ * Local winners.  An executed child of a sequential call command is a local
+ * winner.  In a concurrent step the members are scanned in listed order with
+ * longest = 0; a member's value is hop_ns + duration_ns for an executed call, 0
+ * for a skipped call, max(d, 0) for a sleep; a member takes the lead only when
+ * its value is strictly greater than longest; the step's winner is the last
+ * member that took the lead (it may be a sleep, and there may be none).  So ties
+ * go to the first listed member and a zero-cost child never wins.  A child of a
+ * concurrent step is a local winner iff it is its step's winner.
+ *
+ * Critical set.  The entry is critical; any other span is critical iff it is a
+ * local winner and its caller is critical.
+ *
+ * Self time.  self_ns(v) = duration_ns(v) - the sum over v's local-winner
+ * children c of (hop_ns(c) + duration_ns(c)): the time v spends in its own
+ * sleeps, concurrent steps that a sleep won included.  It is never negative
+ * for the spans of a walk (isim_critical_path_host returns ISIM_EINVAL if it
+ * would be; its outputs are then unspecified).  Mode B needs no extra rule:
+ * nothing follows a failed step, and the spans already say which children ran.
+ *
+ * Identity.  For every trace the sum over its critical spans of (self_ns +
+ * hop_ns) equals the entry's duration_ns, the record's latency_ns.
+ *
+ * The table: (n_services + 1) rows of ISIM_CP_ROW_WORDS u64 words, every word a
+ * sum mod 2^64, so tables merge by plain addition across calls, batches, shards
+ * and GPUs.  Row s < n_services: the words below.  The last row is the header.
+ * Per table the sum over s of (SELF_NS + HOP_NS) equals the header's
+ * ISIM_CP_H_SUM_LATENCY. */
+#define ISIM_SPAN_CRITICAL 4u    /* isim_span.status bit 2: on the critical path (set by isim_critical_path* only) */
+#define ISIM_CP_INVOCATIONS  0   /* every executed invocation of s in the processed traces */
+#define ISIM_CP_SUM_DURATION 1   /* the sum of duration_ns of those invocations */
+#define ISIM_CP_CRITICAL     2   /* invocations of s on the path */
+#define ISIM_CP_SELF_NS      3   /* the sum of self_ns of the critical invocations */
+#define ISIM_CP_HOP_NS       4   /* the sum of hop_ns of the critical invocations: the network time of the calls into s */
+#define ISIM_CP_CRITICAL_500 5   /* critical invocations that responded 500 */
+#define ISIM_CP_ROW_WORDS    6
+/* the header row (row n_services); its last word is 0 */
+#define ISIM_CP_H_TRACES      0  /* traces processed */
+#define ISIM_CP_H_SPANS       1  /* their spans */
+#define ISIM_CP_H_CRITICAL    2  /* their critical spans */
+#define ISIM_CP_H_SUM_LATENCY 3  /* the sum of their entries' duration_ns */
+#define ISIM_CP_H_REFUSED     4  /* traces refused: not the spans of a walk; left untouched, counted nowhere else */
+
+/* host only, no GPU: (n_services + 1) * ISIM_CP_ROW_WORDS */
+ISIM_API int isim_critical_path_table_words(const isim_handler *h, uint64_t *words);
+/* host only, no GPU: 8 bytes per span of the buffer plus 64 */
+ISIM_API int isim_critical_path_workspace_bytes(const isim_handler *h, uint64_t cap_spans, uint64_t *bytes);
+/* host only, no GPU: dst[w] += src[w] over the table's words */
+ISIM_API int isim_critical_path_merge(const isim_handler *h, uint64_t *dst, const uint64_t *src);
+/* The critical path of the d_info[ISIM_SPAN_WRITTEN] traces that a preceding
+ * isim_trace_spans_device of n_ids list entries wrote to d_off / d_spans, on
+ * the current device, asynchronously on hip_stream.  The number of traces is
+ * read on the device (at most n_ids, which bounds the grid).  In place: start_ns
+ * filled as isim_trace_spans_place fills it, ISIM_SPAN_CRITICAL ORed into the
+ * status of the critical spans.  ADDS into d_table (the caller zeroes it).  One
+ * trace per lane: the spans are checked as isim_trace_spans_place checks them
+ * (hop == j, caller_hop < j or the entry's sentinel, position and service in
+ * range; offsets ascending, the range inside cap_spans and inside the written
+ * spans d_off[written], at most 2^32 - 1 spans), a trace that fails is left
+ * untouched and counted in ISIM_CP_H_REFUSED; every index read from a span is
+ * bounded before use.  No host synchronisation, graph-capturable from the first
+ * call, the workspace may be dirty (calls that share one must be ordered); the
+ * first call of a handler on a device uploads the handler's tables, as
+ * isim_trace_spans_device does.  n_ids 0 does nothing.  ISIM_EINVAL, before any
+ * HIP call: the handlers isim_trace_spans_device refuses, a null argument,
+ * n_ids above 2^32, cap_spans above 2^40, buffers not 8-byte aligned, a
+ * workspace below isim_critical_path_workspace_bytes(h, cap_spans). */
+ISIM_API int isim_critical_path_device(const isim_handler *h, const uint64_t *d_off, isim_span *d_spans,
+                                       uint64_t cap_spans, const uint64_t *d_info, uint64_t n_ids, uint64_t *d_table,
+                                       void *d_workspace, uint64_t workspace_bytes, void *hip_stream);
+/* host only, no GPU: the same fold on the CPU over the n_written traces at
+ * h_spans[h_off[i] .. h_off[i + 1]); a trace that reaches past h_off[n_written]
+ * is refused.  ADDS into h_table. */
+ISIM_API int isim_critical_path_host(const isim_handler *h, const uint64_t *h_off, uint64_t n_written,
+                                     isim_span *h_spans, uint64_t *h_table);
+/* Synchronous convenience: host buffers, on GPU `device`. */
+ISIM_API int isim_critical_path(int device, const isim_handler *h, const uint64_t *h_off, uint64_t n_written,
+                                isim_span *h_spans, uint64_t *h_table);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,7 +164,20 @@ struct SpanSink : NoStats {
 // ---- host side (spans.cpp).  "" or why the handler has no spans
 const char *handler_error(const Program &p);
 
-// ---- device side (spans.hip): the launches of one checked call; ISIM_OK or ISIM_EHIP (message set)
+// ---- device side (spans.hip).  The handler's tables on a device: the tree's nodes, per-position facts, the
+// slot-to-callee table and the flat scripts (critical_path.h); uploaded once per (handler, device) at the first
+// call that needs them, under a relaxed capture mode, so that call may itself be a captured one
+struct DevTables {
+  void *nodes = nullptr;
+  TreeExt *ext = nullptr;
+  TreeStep *step = nullptr;
+  uint32_t *slot_callee = nullptr;
+  uint32_t *cmd_off = nullptr;
+  uint64_t *cmds = nullptr;
+};
+int device_tables(const HandlerView &v, DevTables &out);  // of the current device; ISIM_OK or ISIM_EHIP
+
+// the launches of one checked call; ISIM_OK or ISIM_EHIP (message set)
 int spans_launch(const isim_handler *h, const uint64_t *d_ids, uint64_t n_ids, uint64_t *d_off, isim_span *d_spans,
                  uint64_t cap_spans, uint64_t *d_info, void *d_workspace, void *stream);
 int select_launch(const isim_trace_rec *d_records, uint64_t n, uint64_t trace_begin, uint64_t min_latency,

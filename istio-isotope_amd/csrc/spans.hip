@@ -27,6 +27,7 @@
 
 #include "hip_check.h"
 #include "host_stage.h"
+#include "critical_path.h"
 #include "spans.h"
 #include "trace_rec_dev.h"
 
@@ -294,24 +295,19 @@ WalkFn walk_kernel(Frames fr, bool t64, bool modeb, bool wide, bool emit) {
   return pick[fr][t64][modeb](wide, emit);
 }
 
-// ---- the handler's tree on a device: nodes, per-position facts, the slot-to-callee table; uploaded once per
-// (handler, device), kept in the handler (HandlerView::state) and freed with it
-struct DevTables {
-  void *nodes = nullptr;
-  TreeExt *ext = nullptr;
-  TreeStep *step = nullptr;
-  uint32_t *slot_callee = nullptr;
-};
+// ---- the handler's tables on a device (spans.h DevTables), kept in the handler (HandlerView::state) and freed
+// with it
+void free_tables(const DevTables &t) {
+  for (void *q : {t.nodes, (void *)t.ext, (void *)t.step, (void *)t.slot_callee, (void *)t.cmd_off, (void *)t.cmds})
+    if (q) (void)hipFree(q);
+}
 struct State {
   std::map<int, DevTables> dev;
   ~State() {
     int cur = 0;
     const bool have = hipGetDevice(&cur) == hipSuccess;
-    for (auto &kv : dev) {
-      if (hipSetDevice(kv.first) != hipSuccess) continue;
-      for (void *q : {kv.second.nodes, (void *)kv.second.ext, (void *)kv.second.step, (void *)kv.second.slot_callee})
-        if (q) (void)hipFree(q);
-    }
+    for (auto &kv : dev)
+      if (hipSetDevice(kv.first) == hipSuccess) free_tables(kv.second);
     if (have) (void)hipSetDevice(cur);
   }
 };
@@ -330,7 +326,9 @@ int upload(void **dst, const void *src, size_t bytes, hipStream_t s) {
   return ISIM_OK;
 }
 
-int tables_for(const HandlerView &v, DevTables &out) {
+}  // namespace
+
+int device_tables(const HandlerView &v, DevTables &out) {
   int device = 0;
   ISIM_HIPCHK(hipGetDevice(&device));
   std::lock_guard<std::mutex> lk(*v.mu);
@@ -343,6 +341,7 @@ int tables_for(const HandlerView &v, DevTables &out) {
   }
   const Program &p = *v.prog;
   const std::vector<uint32_t> callee(p.slot_callee.begin(), p.slot_callee.end());
+  const cp::FlatScripts scripts = cp::flat_scripts(*v.graph);
   RelaxedCapture relaxed;
   hipStream_t s = nullptr;
   ISIM_HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -352,19 +351,18 @@ int tables_for(const HandlerView &v, DevTables &out) {
   if (rc == ISIM_OK) rc = upload((void **)&t.ext, p.tree_ext.data(), p.tree_ext.size() * sizeof(TreeExt), s);
   if (rc == ISIM_OK) rc = upload((void **)&t.step, p.tree_step.data(), p.tree_step.size() * sizeof(TreeStep), s);
   if (rc == ISIM_OK) rc = upload((void **)&t.slot_callee, callee.data(), callee.size() * sizeof(uint32_t), s);
+  if (rc == ISIM_OK) rc = upload((void **)&t.cmd_off, scripts.cmd_off.data(), scripts.cmd_off.size() * sizeof(uint32_t), s);
+  if (rc == ISIM_OK) rc = upload((void **)&t.cmds, scripts.cmds.data(), scripts.cmds.size() * sizeof(uint64_t), s);
   if (rc == ISIM_OK && hipStreamSynchronize(s) != hipSuccess) rc = set_error(ISIM_EHIP, "trace spans: table upload failed");
   (void)hipStreamDestroy(s);
   if (rc != ISIM_OK) {
-    for (void *q : {t.nodes, (void *)t.ext, (void *)t.step, (void *)t.slot_callee})
-      if (q) (void)hipFree(q);
+    free_tables(t);
     return rc;
   }
   st.dev.emplace(device, t);
   out = t;
   return ISIM_OK;
 }
-
-}  // namespace
 
 int spans_launch(const isim_handler *h, const uint64_t *d_ids, uint64_t n_ids, uint64_t *d_off, isim_span *d_spans,
                  uint64_t cap_spans, uint64_t *d_info, void *d_workspace, void *stream) {
@@ -379,7 +377,7 @@ int spans_launch(const isim_handler *h, const uint64_t *d_ids, uint64_t n_ids, u
     return ISIM_OK;
   }
   DevTables t;
-  if (const int rc = tables_for(v, t)) return rc;
+  if (const int rc = device_tables(v, t)) return rc;
   unsigned long long *work = (unsigned long long *)(wsp + ws.off_work);
   WK k{};
   k.ids = d_ids;

@@ -72,6 +72,11 @@ CL_INFO_WORDS = 4
 SPAN_TOTAL, SPAN_WRITTEN, SPAN_N_IDS, SPAN_FIRST_UNFIT = 0, 1, 2, 3
 SPAN_INFO_WORDS = 4
 SPAN_NONE = 0xFFFFFFFF  # the entry's caller_hop and slot
+# isim_critical_path*: the status bit, the words of a service row and of the header row (isim.h ISIM_CP_*)
+SPAN_CRITICAL = 4
+CP_INVOCATIONS, CP_SUM_DURATION, CP_CRITICAL, CP_SELF_NS, CP_HOP_NS, CP_CRITICAL_500 = range(6)
+CP_ROW_WORDS = 6
+CP_H_TRACES, CP_H_SPANS, CP_H_CRITICAL, CP_H_SUM_LATENCY, CP_H_REFUSED = range(5)
 
 
 def SK_BINS(s: int) -> int:
@@ -262,6 +267,12 @@ SIGNATURES = {
     "isim_select_traces": (C.c_int, [C.c_int, _VP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, _VP,
                                      _VP]),
     "isim_select_traces_host": (C.c_int, [_VP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, _VP, _VP]),
+    "isim_critical_path_table_words": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
+    "isim_critical_path_workspace_bytes": (C.c_int, [_VP, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "isim_critical_path_merge": (C.c_int, [_VP, _VP, _VP]),
+    "isim_critical_path_device": (C.c_int, [_VP, _VP, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP]),
+    "isim_critical_path_host": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP]),
+    "isim_critical_path": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, _VP, _VP]),
 }
 
 _lib = None

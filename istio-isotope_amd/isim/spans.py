@@ -5,6 +5,8 @@
     for t in ts.slowest(recs, 0):                    # the traces at or above p99.9, at most 64
         print(t.to_text())
     t = ts.spans([12345])[0]                         # any trace, from its id alone
+    cp = ts.tail_critical_path(recs, 0)              # across the tail: which services hold the latency (§20)
+    print(cp.to_text())
 
 A dynamic walk keeps 16 bytes per trace; a trace is a pure function of (seed,
 trace id), so the calls behind any record come from walking that id again, in
@@ -67,6 +69,11 @@ def select_traces_host(records, trace_begin: int, min_latency_ns: int, cls: int 
     return _select(native.load().isim_select_traces_host, (), records, trace_begin, min_latency_ns, cls, max_ids)
 
 
+def _i64(words, dev):
+    import torch
+    return torch.zeros(max(1, words), dtype=torch.int64, device=dev)
+
+
 class Trace:
     """One trace: its id, its spans (a SPAN_DTYPE array ordered by hop) and the graph's service names."""
 
@@ -80,8 +87,13 @@ class Trace:
     def __len__(self) -> int:
         return len(self.spans)
 
+    def critical(self) -> np.ndarray:
+        """The hops on the critical path (set by TraceSpans.critical_path*; empty before)."""
+        return np.flatnonzero(self.spans["status"] & native.SPAN_CRITICAL)
+
     def to_text(self) -> str:
-        """An indented tree: service, status, start and duration per executed invocation."""
+        """An indented tree: service, status, start and duration per executed invocation; a span on the
+        critical path ends in " *"."""
         s = self.spans
         depth = np.zeros(len(s), np.int64)
         lines = [f"trace {self.trace_id}: {len(s)} spans, {self.latency_ns} ns"]
@@ -91,7 +103,60 @@ class Trace:
             st = int(s["status"][i])
             code = "200" if not st & 1 else ("500" if st & 2 else "500 (failed step)")
             lines.append(f"{'  ' * int(depth[i])}{self.names[int(s['service'][i])]} {code} "
-                         f"start={int(s['start_ns'][i])} hop={int(s['hop_ns'][i])} dur={int(s['duration_ns'][i])}")
+                         f"start={int(s['start_ns'][i])} hop={int(s['hop_ns'][i])} dur={int(s['duration_ns'][i])}"
+                         f"{' *' if st & native.SPAN_CRITICAL else ''}")
+        return "\n".join(lines)
+
+
+CP_WORDS = ("invocations", "sum_duration_ns", "critical", "self_ns", "hop_ns", "critical_500")
+
+
+class CriticalPath:
+    """A critical-path table (DESIGN.md §20): per service the six ISIM_CP_* words, then the header row;
+    every word a sum mod 2^64, so tables of calls, batches, shards and GPUs merge by addition.  traces:
+    the marked Traces, where the call kept them."""
+
+    def __init__(self, handler, table: np.ndarray, names: Sequence[str], traces: List[Trace] = None):
+        self.handler, self.names, self.traces = handler, names, list(traces or [])
+        self.table = np.ascontiguousarray(table, dtype=np.uint64).reshape(len(names) + 1, native.CP_ROW_WORDS)
+
+    @property
+    def header(self) -> dict:
+        h = self.table[-1]
+        return dict(traces=int(h[native.CP_H_TRACES]), spans=int(h[native.CP_H_SPANS]),
+                    critical=int(h[native.CP_H_CRITICAL]), sum_latency_ns=int(h[native.CP_H_SUM_LATENCY]),
+                    refused=int(h[native.CP_H_REFUSED]))
+
+    def rows(self) -> List[dict]:
+        """Per service with an invocation: its name, the six words and its share of the latency (SELF_NS +
+        HOP_NS over the header's sum), sorted by that time, the largest first."""
+        total = self.header["sum_latency_ns"]
+        out = []
+        for name, r in zip(self.names, self.table[:-1]):
+            if not int(r[native.CP_INVOCATIONS]):
+                continue
+            d = dict(service=name, **{w: int(x) for w, x in zip(CP_WORDS, r)})
+            d["path_ns"] = d["self_ns"] + d["hop_ns"]
+            d["share"] = d["path_ns"] / total if total else 0.0
+            out.append(d)
+        return sorted(out, key=lambda d: -d["path_ns"])
+
+    def merge(self, other: "CriticalPath") -> "CriticalPath":
+        """Adds other's table (isim_critical_path_merge) and takes its traces along."""
+        assert self.table.shape == other.table.shape
+        native.check(native.load().isim_critical_path_merge(self.handler._h, self.table.ctypes.data,
+                                                            other.table.ctypes.data))
+        self.traces += other.traces
+        return self
+
+    def to_text(self, top: int = None) -> str:
+        h = self.header
+        lines = [f"critical path of {h['traces']} traces: {h['critical']} of {h['spans']} spans, "
+                 f"{h['sum_latency_ns']} ns" + (f", {h['refused']} refused" if h["refused"] else ""),
+                 f"{'service':<24}{'share':>8}{'self_ns':>16}{'hop_ns':>14}{'critical':>10}{'of':>10}{'500':>8}"]
+        for d in self.rows()[:top]:
+            lines.append(f"{d['service']:<24}{100 * d['share']:>7.2f}%{d['self_ns']:>16}{d['hop_ns']:>14}"
+                         f"{d['critical']:>10}{d['invocations']:>10}{d['critical_500']:>8}")
         return "\n".join(lines)
 
 
@@ -164,6 +229,89 @@ class TraceSpans:
         native.check(native.load().isim_trace_spans_place(self.handler._h, off.ctypes.data, n_written,
                                                           spans.ctypes.data))
 
+    # ---- the critical path
+    def table_words(self) -> int:
+        w = C.c_uint64()
+        native.check(native.load().isim_critical_path_table_words(self.handler._h, C.byref(w)))
+        return int(w.value)
+
+    def critical_path_workspace_bytes(self, cap_spans: int) -> int:
+        b = C.c_uint64()
+        native.check(native.load().isim_critical_path_workspace_bytes(self.handler._h, cap_spans, C.byref(b)))
+        return int(b.value)
+
+    def fold_host(self, off: np.ndarray, spans: np.ndarray, n_written: int, table: np.ndarray = None) -> np.ndarray:
+        """isim_critical_path_host over host spans, in place (start_ns, the critical bit); adds into table
+        (a new one of zeros when None) and returns it."""
+        if table is None:
+            table = np.zeros(self.table_words(), np.uint64)
+        native.check(native.load().isim_critical_path_host(self.handler._h, off.ctypes.data, n_written,
+                                                           spans.ctypes.data, table.ctypes.data))
+        return table
+
+    def fold(self, off: np.ndarray, spans: np.ndarray, n_written: int, table: np.ndarray = None,
+             device: int = 0) -> np.ndarray:
+        """The same through isim_critical_path: on the GPU, synchronous, over host buffers."""
+        if table is None:
+            table = np.zeros(self.table_words(), np.uint64)
+        native.check(native.load().isim_critical_path(device, self.handler._h, off.ctypes.data, n_written,
+                                                      spans.ctypes.data, table.ctypes.data))
+        return table
+
+    def critical_path(self, ids, device: int = 0) -> CriticalPath:
+        """Synchronous, on the GPU: the spans of the listed traces and their critical path."""
+        ids, off, spans, info = self._raw(native.load().isim_trace_spans, (device,), ids, None)
+        written = int(info[native.SPAN_WRITTEN])
+        table = self.fold(off, spans, written, device=device)
+        return CriticalPath(self.handler, table, self.names, self._split(ids, off, spans, written))
+
+    def critical_path_host(self, ids) -> CriticalPath:
+        """The same on the host (no GPU)."""
+        ids, off, spans, info = self._raw(native.load().isim_trace_spans_host, (), ids, None)
+        written = int(info[native.SPAN_WRITTEN])
+        table = self.fold_host(off, spans, written)
+        return CriticalPath(self.handler, table, self.names, self._split(ids, off, spans, written))
+
+    def critical_path_device(self, *, d_off: int, d_spans: int, cap_spans: int, d_info: int, n_ids: int, d_table: int,
+                             d_workspace: int, workspace_bytes: int = None, stream: int = 0) -> None:
+        """Asynchronous on the current HIP device, after a spans_device call of n_ids entries with the
+        same d_off, d_spans, cap_spans and d_info: fills start_ns, marks the critical spans and ADDS into
+        d_table (table_words() u64, zeroed by the caller); d_workspace:
+        critical_path_workspace_bytes(cap_spans) bytes, dirty or not."""
+        if workspace_bytes is None:
+            workspace_bytes = self.critical_path_workspace_bytes(cap_spans)
+        native.check(native.load().isim_critical_path_device(self.handler._h, d_off or None, d_spans or None,
+                                                             cap_spans, d_info or None, n_ids, d_table or None,
+                                                             d_workspace or None, workspace_bytes, stream or None))
+
+    def _tail_ids(self, records, trace_begin, q_ppm, cls, max_traces, dev, stream):
+        """(ids as a device tensor, how many) of the records at or above their exact q_ppm latency quantile
+        in class cls, the first max_traces (None: all) in trace order: the quantile select and the trace
+        select on `stream`.  Call with `dev` current."""
+        import torch
+        if isinstance(records, torch.Tensor):
+            d_recs, n = records, records.numel() * records.element_size() // REC_DTYPE.itemsize
+        else:
+            recs = np.ascontiguousarray(records, dtype=REC_DTYPE)
+            n = len(recs)
+            d_recs = torch.from_numpy(recs.view(np.int64).copy()).to(dev)
+        if n == 0:
+            return None, 0
+        keep = n if max_traces is None else min(int(max_traces), n)
+        q = (q_ppm / 1e6,)
+        qout = _i64(quantiles_out_words(1), dev)
+        qws = torch.empty(quantiles_workspace_bytes(1), dtype=torch.uint8, device=dev)
+        latency_quantiles_device(d_recs.data_ptr(), n, q, d_out=qout.data_ptr(), d_workspace=qws.data_ptr(),
+                                 stream=stream)
+        # the select takes its threshold by value: the one word the host reads between the steps
+        thr = int(qout.cpu().numpy().view(np.uint64).reshape(3, 2)[cls, 1])
+        ids, sinfo = _i64(keep, dev), _i64(2, dev)
+        sws = torch.empty(select_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        select_traces_device(d_recs.data_ptr(), n, trace_begin, thr, cls, max_ids=keep,
+                             d_ids=ids.data_ptr(), d_info=sinfo.data_ptr(), d_workspace=sws.data_ptr(),
+                             stream=stream)
+        return ids, int(sinfo.cpu().numpy().view(np.uint64)[1])
+
     def slowest(self, records, trace_begin: int, q_ppm: int = 999000, cls: int = native.Q_ALL, max_traces: int = 64,
                 device: int = 0) -> List[Trace]:
         """The traces of a served batch at or above its exact q_ppm latency quantile in class cls (the
@@ -173,34 +321,10 @@ class TraceSpans:
         dev = torch.device("cuda", device)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            if isinstance(records, torch.Tensor):
-                d_recs, n = records, records.numel() * records.element_size() // REC_DTYPE.itemsize
-            else:
-                recs = np.ascontiguousarray(records, dtype=REC_DTYPE)
-                n = len(recs)
-                d_recs = torch.from_numpy(recs.view(np.int64).copy()).to(dev)
-            if n == 0:
-                return []
-
-            def i64(words):
-                return torch.zeros(max(1, words), dtype=torch.int64, device=dev)
-
-            q = (q_ppm / 1e6,)
-            qout = i64(quantiles_out_words(1))
-            qws = torch.empty(quantiles_workspace_bytes(1), dtype=torch.uint8, device=dev)
-            latency_quantiles_device(d_recs.data_ptr(), n, q, d_out=qout.data_ptr(), d_workspace=qws.data_ptr(),
-                                     stream=stream)
-            # the select takes its threshold by value: the one word the host reads between the steps
-            thr = int(qout.cpu().numpy().view(np.uint64).reshape(3, 2)[cls, 1])
-            ids, sinfo = i64(max_traces), i64(2)
-            sws = torch.empty(select_workspace_bytes(n), dtype=torch.uint8, device=dev)
-            select_traces_device(d_recs.data_ptr(), n, trace_begin, thr, cls, max_ids=max_traces,
-                                 d_ids=ids.data_ptr(), d_info=sinfo.data_ptr(), d_workspace=sws.data_ptr(),
-                                 stream=stream)
-            m = int(sinfo.cpu().numpy().view(np.uint64)[1])
+            ids, m = self._tail_ids(records, trace_begin, q_ppm, cls, max_traces, dev, stream)
             if m == 0:
                 return []
-            off, info = i64(m + 1), i64(native.SPAN_INFO_WORDS)
+            off, info = _i64(m + 1, dev), _i64(native.SPAN_INFO_WORDS, dev)
             wsb = self.workspace_bytes(m)
             ws = torch.empty(max(1, wsb), dtype=torch.uint8, device=dev)
             cap = min(m * max(1, int(self.handler.info.hops_upper)), 1 << 20)
@@ -219,3 +343,52 @@ class TraceSpans:
             h_ids = ids.cpu().numpy().view(np.uint64)[:m].copy()
         self.place(h_off, h_spans, m)
         return self._split(h_ids, h_off, h_spans, m)
+
+    def tail_critical_path(self, records, trace_begin: int, q_ppm: int = 999000, cls: int = native.Q_ALL,
+                           max_traces: int = None, cap_spans: int = 1 << 20, keep_traces: bool = False,
+                           device: int = 0) -> CriticalPath:
+        """The critical path across the tail of a served batch: the traces at or above its exact q_ppm
+        latency quantile in class cls (all of them, or the first max_traces in trace order).  Four steps
+        on one stream of the device: quantile, select, spans, critical path; the last two in chunks of
+        what a buffer of cap_spans spans holds (the next chunk starts at ISIM_SPAN_FIRST_UNFIT), all
+        adding into one table.  keep_traces: the marked Traces come along (copied to the host)."""
+        import torch
+        dev = torch.device("cuda", device)
+        words = self.table_words()
+        traces: List[Trace] = []
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            ids, m = self._tail_ids(records, trace_begin, q_ppm, cls, max_traces, dev, stream)
+            table = _i64(words, dev)
+            cap, pos = max(1, int(cap_spans)), 0
+            bufs = None
+            while pos < m:
+                if bufs is None:    # (again after a trace that alone needs more than cap spans)
+                    per = min(m, cap)       # every trace has a span: a chunk holds at most cap traces
+                    off, info = _i64(per + 1, dev), _i64(native.SPAN_INFO_WORDS, dev)
+                    spans = torch.empty(cap * SPAN_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                    sws_b, cws_b = self.workspace_bytes(per), self.critical_path_workspace_bytes(cap)
+                    sws = torch.empty(max(1, sws_b), dtype=torch.uint8, device=dev)
+                    cws = torch.empty(cws_b, dtype=torch.uint8, device=dev)
+                    bufs = True
+                n_ids = min(m - pos, per)
+                self.spans_device(ids.data_ptr() + 8 * pos, n_ids, d_off=off.data_ptr(), d_spans=spans.data_ptr(),
+                                  cap_spans=cap, d_info=info.data_ptr(), d_workspace=sws.data_ptr(),
+                                  workspace_bytes=sws_b, stream=stream)
+                self.critical_path_device(d_off=off.data_ptr(), d_spans=spans.data_ptr(), cap_spans=cap,
+                                          d_info=info.data_ptr(), n_ids=n_ids, d_table=table.data_ptr(),
+                                          d_workspace=cws.data_ptr(), workspace_bytes=cws_b, stream=stream)
+                # the host reads where the next chunk starts: one word per chunk
+                first_unfit = int(info.cpu().numpy().view(np.uint64)[native.SPAN_FIRST_UNFIT])
+                if first_unfit == 0:    # not one trace fits: room for the first, and the chunk again
+                    cap = int(off[1].item())
+                    bufs = None
+                    continue
+                if keep_traces:
+                    h_off = off[:first_unfit + 1].cpu().numpy().view(np.uint64).copy()
+                    h_spans = spans[:int(h_off[-1]) * SPAN_DTYPE.itemsize].cpu().numpy().view(SPAN_DTYPE).copy()
+                    h_ids = ids[pos:pos + first_unfit].cpu().numpy().view(np.uint64).copy()
+                    traces += self._split(h_ids, h_off, h_spans, first_unfit)
+                pos += first_unfit
+            h_table = table.cpu().numpy().view(np.uint64).copy()
+        return CriticalPath(self.handler, h_table, self.names, traces)
