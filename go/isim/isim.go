@@ -334,6 +334,83 @@ func (h *Handler) CriticalPath(device int, ids []uint64) ([][]Span, []uint64, er
 	return traces, table, nil
 }
 
+// DesSpan is one executed invocation of a trace of a DES batch (isim_des_span,
+// DESIGN §21): it reached its replica's queue at arrival_ns, the worker took it
+// at start_ns and it responded at finish_ns, all on the batch clock.
+type DesSpan = C.isim_des_span
+
+// The DES wait table (DESIGN §21): (services + 1) rows of DwRowWords words over
+// the emitted spans; tables merge by addition except DwMaxWait (DesWaitMerge).
+const (
+	DesSpanMatches = C.ISIM_DES_SPAN_MATCHES
+	DwInvocations  = C.ISIM_DW_INVOCATIONS
+	DwWaited       = C.ISIM_DW_WAITED
+	DwSumWait      = C.ISIM_DW_SUM_WAIT
+	DwMaxWait      = C.ISIM_DW_MAX_WAIT
+	DwSumDuration  = C.ISIM_DW_SUM_DURATION
+	DwResp500      = C.ISIM_DW_RESP_500
+	DwRowWords     = C.ISIM_DW_ROW_WORDS
+	DwHTraces      = C.ISIM_DW_H_TRACES
+	DwHSpans       = C.ISIM_DW_H_SPANS
+	DwHSumLatency  = C.ISIM_DW_H_SUM_LATENCY
+	DwHSumWait     = C.ISIM_DW_H_SUM_WAIT
+)
+
+// ServeDesSpans runs one DES batch under the constant mean gap meanNs on GPU
+// `device` and returns its records and, for the traces at or above the batch's
+// qPpm order statistic (at most maxTraces whose spans fit capSpans), their
+// invocations with queue times, and the wait table (isim_serve_des_spans).  The
+// handler's DES must run on the item engine (ISIM_FLAG_DYNAMIC).
+func (h *Handler) ServeDesSpans(device int, meanNs, begin uint64, n int, qPpm uint32, maxTraces, capSpans int) ([]TraceRecord, [][]DesSpan, []uint64, error) {
+	var words C.uint64_t
+	if err := lastErr(C.isim_des_wait_table_words(h.h, &words)); err != nil {
+		return nil, nil, nil, err
+	}
+	if maxTraces > n {
+		maxTraces = n
+	}
+	recs := make([]TraceRecord, n+1)
+	// the tap's buffers live in C memory for the call (a struct passed to C may hold no Go pointers)
+	nInfo := int(C.ISIM_DES_SPAN_INFO_WORDS)
+	sizes := []int{8 * (maxTraces + 1), 8 * (maxTraces + 1), int(unsafe.Sizeof(DesSpan{})) * (capSpans + 1), 8 * nInfo, 8 * int(words)}
+	bufs := make([]unsafe.Pointer, len(sizes))
+	for i, b := range sizes {
+		bufs[i] = C.calloc(1, C.size_t(b))
+		defer C.free(bufs[i])
+	}
+	tap := (*C.isim_des_tap)(C.calloc(1, C.size_t(unsafe.Sizeof(C.isim_des_tap{}))))
+	defer C.free(unsafe.Pointer(tap))
+	tap.q_ppm = C.uint32_t(qPpm)
+	tap.cls = C.ISIM_Q_ALL
+	tap.max_traces = C.uint64_t(maxTraces)
+	tap.cap_spans = C.uint64_t(capSpans)
+	tap.d_ids = (*C.uint64_t)(bufs[0])
+	tap.d_off = (*C.uint64_t)(bufs[1])
+	tap.d_spans = (*C.isim_des_span)(bufs[2])
+	tap.d_info = (*C.uint64_t)(bufs[3])
+	tap.d_wait_table = (*C.uint64_t)(bufs[4])
+	p := C.isim_des_params{mean_interarrival_ns: C.uint64_t(meanNs)}
+	rc := C.isim_serve_des_spans(h.h, C.int(device), &p, nil, C.uint64_t(begin), C.uint64_t(n), &recs[0], nil, nil, tap)
+	if err := lastErr(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	info := (*[1 << 3]uint64)(bufs[3])[:nInfo:nInfo]
+	off := (*[1 << 30]uint64)(bufs[1])[: maxTraces+1 : maxTraces+1]
+	written := int(info[C.ISIM_SPAN_WRITTEN])
+	all := append([]DesSpan(nil), (*[1 << 24]DesSpan)(bufs[2])[:off[written]:off[written]]...)
+	out := make([][]DesSpan, written)
+	for i := range out {
+		out[i] = all[off[i]:off[i+1]]
+	}
+	table := append([]uint64(nil), (*[1 << 30]uint64)(bufs[4])[:words:words]...)
+	return recs[:n], out, table, nil
+}
+
+// DesWaitMerge adds src into dst (isim_des_wait_merge): sums, DwMaxWait by max.
+func (h *Handler) DesWaitMerge(dst, src []uint64) error {
+	return lastErr(C.isim_des_wait_merge(h.h, u64ptr(dst), u64ptr(src)))
+}
+
 // SelectTraces returns the ids begin + i of the records with a latency of at
 // least minLatencyNs in class cls (C.ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500), in
 // ascending i, at most maxIDs of them, and the number of matching records

@@ -994,6 +994,109 @@ ISIM_API int isim_critical_path_host(const isim_handler *h, const uint64_t *h_of
 ISIM_API int isim_critical_path(int device, const isim_handler *h, const uint64_t *h_off, uint64_t n_written,
                                 isim_span *h_spans, uint64_t *h_table);
 
+/* ---- DES trace spans: where the slow traces of a contended batch waited (EXT) ----
+ * Under the DES an invocation's queue wait depends on every other trace of the
+ * batch, so a trace cannot be walked again later: its arrival, start and finish
+ * exist only in the item engine's per-batch arrays.  A tap on a DES batch
+ * writes them out for chosen traces before the batch ends, and folds their
+ * waits into a per-service table.  Item engine only (isim_des_info.items == 1:
+ * a dynamic walk, or any graph under ISIM_FLAG_DYNAMIC).
+ *
+ * The spans of one trace are contiguous and in hop order.  All three times are
+ * on the batch clock of isim_des_arrivals* (time 0 = the batch start).  The
+ * entry's arrival_ns is the trace's A_t, its finish_ns - arrival_ns the
+ * record's latency_ns.  With duration = finish_ns - arrival_ns next to hop_ns,
+ * the winner rule of isim_critical_path (hop_ns + duration) reads unchanged. */
+typedef struct {
+  uint64_t arrival_ns;   /* a: the request reaches the replica's queue */
+  uint64_t start_ns;     /* S: the worker takes it; S - a is the queue wait */
+  uint64_t finish_ns;    /* F: the respond point */
+  uint64_t hop_ns;       /* H of the call site; entry 0 */
+  uint32_t hop;          /* as isim_span; entry 0 */
+  uint32_t caller_hop;   /* as isim_span; 0xFFFFFFFF for the entry */
+  uint32_t position;     /* as isim_span */
+  uint32_t slot;         /* as isim_span; 0xFFFFFFFF for the entry */
+  uint32_t service;      /* as isim_span */
+  uint32_t status;       /* as isim_span: bit 0 responded 500, bit 1 its own error draw */
+  uint32_t replica;      /* the replica the §10.1 draw chose; 0 when the service has one */
+  uint32_t reserved;     /* 0 */
+} isim_des_span;         /* 64 bytes */
+
+/* d_info: the four words of isim_trace_spans_device (ISIM_SPAN_TOTAL, _WRITTEN,
+ * _N_IDS, _FIRST_UNFIT over the chosen list) and the matches before max_traces cut it */
+#define ISIM_DES_SPAN_MATCHES 4
+#define ISIM_DES_SPAN_INFO_WORDS 5
+
+/* The wait table: (n_services + 1) rows of ISIM_DW_ROW_WORDS u64 words, ADDED
+ * into (the caller zeroes it).  Row s < n_services, over the emitted spans of
+ * service s: the words below.  The last row is the header.  Tables merge by
+ * addition, except ISIM_DW_MAX_WAIT, which merges by MAX (isim_des_wait_merge). */
+#define ISIM_DW_INVOCATIONS  0   /* emitted spans of s */
+#define ISIM_DW_WAITED       1   /* those with S > a */
+#define ISIM_DW_SUM_WAIT     2   /* sum of S - a */
+#define ISIM_DW_MAX_WAIT     3   /* largest S - a */
+#define ISIM_DW_SUM_DURATION 4   /* sum of F - a */
+#define ISIM_DW_RESP_500     5   /* those that responded 500 */
+#define ISIM_DW_ROW_WORDS    6
+/* the header row (row n_services); its last two words are 0 */
+#define ISIM_DW_H_TRACES      0  /* traces emitted */
+#define ISIM_DW_H_SPANS       1  /* their spans */
+#define ISIM_DW_H_SUM_LATENCY 2  /* the sum of their entries' F - a (the records' latency_ns) */
+#define ISIM_DW_H_SUM_WAIT    3  /* the sum of their entries' own S - a */
+
+/* Which traces, and where their spans go.  Chosen: the batch's records with
+ * latency_ns >= threshold in class cls, ids ascending, the first max_traces of
+ * them.  The threshold is min_latency_ns when q_ppm is 0; otherwise the exact
+ * order statistic isim_quantile_rank(N_cls, q_ppm) of this batch's records in
+ * that class (isim_latency_quantiles_device on the same stream; the host reads
+ * that one word).  A trace's span count is its record's hops; the counts are
+ * scanned into d_off; a trace whose range ends past cap_spans writes nothing,
+ * so the traces that fit are a prefix of the list.  Words of d_ids and d_off
+ * past the chosen list, and spans past d_off[written], are left untouched. */
+typedef struct {
+  uint64_t min_latency_ns;   /* the threshold when q_ppm == 0 */
+  uint32_t q_ppm;            /* 0, or 1 .. 1000000 */
+  uint32_t cls;              /* ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500 */
+  uint64_t max_traces;       /* <= 2^32 */
+  uint64_t cap_spans;        /* <= 2^40 */
+  uint64_t *d_ids;           /* [max_traces] (may be NULL when max_traces is 0) */
+  uint64_t *d_off;           /* [max_traces + 1] */
+  isim_des_span *d_spans;    /* [cap_spans] (may be NULL when cap_spans is 0) */
+  uint64_t *d_info;          /* [ISIM_DES_SPAN_INFO_WORDS], written */
+  uint64_t *d_wait_table;    /* NULL, or (n_services + 1) * ISIM_DW_ROW_WORDS words, added into */
+  uint64_t reserved[2];      /* 0 */
+} isim_des_tap;
+
+/* host only, no GPU: (n_services + 1) * ISIM_DW_ROW_WORDS */
+ISIM_API int isim_des_wait_table_words(const isim_handler *h, uint64_t *words);
+/* host only, no GPU: dst += src, ISIM_DW_MAX_WAIT of the service rows by MAX */
+ISIM_API int isim_des_wait_merge(const isim_handler *h, uint64_t *dst, const uint64_t *src);
+/* One DES batch as isim_serve_des_device runs it (lp NULL: the constant mean
+ * of p) or as isim_serve_des_profile_device runs it (lp given: p->flags are the
+ * des_flags, p's mean is not read), with the same workspace.  With a NULL tap
+ * it IS that call: records, stats and table bit for bit.  With a tap,
+ * d_records is required, and the tap's kernels follow the batch on hip_stream
+ * while its item arrays are alive; they do not walk the tree again.  The call
+ * synchronises with the host as every item-engine batch does.  A batch that is
+ * not accumulated (a look-back fault, or ISIM_ST_DES_RETRY) writes d_off[0] = 0
+ * and a d_info with no trace written, no span and nothing to the table.
+ * n_traces 0 with a tap does the same.  ISIM_EINVAL, before any HIP call: what
+ * the two calls above refuse; with a tap: a handler whose DES is not on the
+ * item engine (create it with ISIM_FLAG_DYNAMIC), null records, null or
+ * misaligned tap buffers (8 bytes; d_spans 16), max_traces above 2^32,
+ * cap_spans above 2^40, a class out of range, q_ppm above 1000000, nonzero
+ * reserved words. */
+ISIM_API int isim_serve_des_spans_device(isim_handler *h, const isim_des_params *p, const isim_load_profile *lp,
+                                         uint64_t trace_begin, uint64_t n_traces, isim_trace_rec *d_records,
+                                         uint64_t *d_stats, uint64_t *d_des_table, void *d_workspace,
+                                         uint64_t workspace_bytes, const isim_des_tap *tap, void *hip_stream);
+/* Synchronous convenience: host buffers, the tap's five pointers included (its
+ * wait table is added into as well); h_records, h_stats and h_des_table may be NULL. */
+ISIM_API int isim_serve_des_spans(isim_handler *h, int device, const isim_des_params *p,
+                                  const isim_load_profile *lp, uint64_t trace_begin, uint64_t n_traces,
+                                  isim_trace_rec *h_records, uint64_t *h_stats, uint64_t *h_des_table,
+                                  const isim_des_tap *tap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1008,6 +1008,7 @@ struct DesLoad {
   const isim::lp::Compiled *profile;  // null: mean_ns
   uint64_t horizon;                   // profile: no arrival of the batch passes it (< 2^62)
   uint32_t flags;                     // 0 or ISIM_DES_FLAG_WIDE
+  const isim_des_tap *tap = nullptr;  // the span tap: item engine only, checked by the caller
 };
 
 int serve_des_device(isim_handler *h, const DesLoad &load, uint64_t trace_begin, uint64_t n_traces,
@@ -1136,6 +1137,14 @@ int serve_des_device(isim_handler *h, const DesLoad &load, uint64_t trace_begin,
     L.pool = st->des_pool;
     isim::DesItemsReport rep{};
     L.report = &rep;
+    if (load.tap) {  // the slot-to-callee table of the span code (uploaded once per handler and device)
+      isim::spans::DevTables t;
+      if (const int trc = isim::spans::device_tables(isim::spans::handler_view(h), t)) return trc;
+      L.tap = load.tap;
+      L.d_slot_callee = t.slot_callee;
+      L.entry_service = (uint32_t)h->prog.entry;
+      L.n_services = (uint32_t)h->prog.n_services;
+    }
     if (const int urc = upload_profile(L.profile)) return urc;
     std::string e;
     const int irc = isim::des_items_launch(L, hip_stream, e);
@@ -1199,7 +1208,7 @@ int serve_des_device(isim_handler *h, const DesLoad &load, uint64_t trace_begin,
 // enqueues it with the given row flags (isim_serve_des_device, or the profile twin).
 template <typename Enqueue>
 int serve_des_host(isim_handler *h, int device, uint32_t flags0, uint64_t n_traces, isim_trace_rec *h_records,
-                   uint64_t *h_stats, uint64_t *h_des_table, Enqueue enqueue) {
+                   uint64_t *h_stats, uint64_t *h_des_table, Enqueue enqueue, bool device_records = false) {
   int prev = 0;
   HIPCHK(hipGetDevice(&prev));
   HIPCHK(hipSetDevice(device));
@@ -1219,7 +1228,7 @@ int serve_des_host(isim_handler *h, int device, uint32_t flags0, uint64_t n_trac
       rc = fail(ISIM_EHIP, "hipMalloc(DES buffers) failed");
       break;
     }
-    if (h_records && n_traces && hipMalloc(&d_rec, n_traces * sizeof(isim_trace_rec)) != hipSuccess) {
+    if ((h_records || device_records) && n_traces && hipMalloc(&d_rec, n_traces * sizeof(isim_trace_rec)) != hipSuccess) {
       rc = fail(ISIM_EHIP, "hipMalloc(records) failed");
       break;
     }
@@ -1262,7 +1271,7 @@ int serve_des_host(isim_handler *h, int device, uint32_t flags0, uint64_t n_trac
       rc = fail(ISIM_EHIP, "copy DES table failed");
       break;
     }
-    if (d_rec && hipMemcpyAsync(h_records, d_rec, n_traces * sizeof(isim_trace_rec), hipMemcpyDeviceToHost, s) !=
+    if (d_rec && h_records && hipMemcpyAsync(h_records, d_rec, n_traces * sizeof(isim_trace_rec), hipMemcpyDeviceToHost, s) !=
                      hipSuccess) {
       rc = fail(ISIM_EHIP, "copy records failed");
       break;
@@ -1484,6 +1493,149 @@ int isim_des_fold(const isim_handler *h, const uint64_t *des_table, uint64_t *sv
   for (size_t r = 0; r < p.row_svc.size(); ++r)
     std::copy(des_table + r * W, des_table + (r + 1) * W, svc_rows + (size_t)p.row_svc[r] * W);
   return ISIM_OK;
+}
+
+}  // extern "C"
+
+// ---- DES trace spans: the tap on an item-engine batch (des_items.hip)
+namespace {
+
+int tfail(const std::string &msg) { return fail(ISIM_EINVAL, "DES spans: " + msg); }
+
+// every check of a tap that needs no GPU; `aligned`: the five pointers are device buffers
+int des_tap_check(const isim_handler *h, const isim_des_tap *tap, bool have_records, bool aligned) {
+  if (const int drc = des_ensure(h)) return drc;
+  if (!h->des.items)
+    return tfail("this handler's DES runs on the static engine, which keeps no invocations: create the handler "
+                 "with ISIM_FLAG_DYNAMIC");
+  if (!have_records) return tfail("a tap needs d_records");
+  if (tap->reserved[0] || tap->reserved[1]) return tfail("isim_des_tap.reserved must be 0");
+  if (tap->cls > ISIM_Q_500) return tfail("the class must be ISIM_Q_ALL, ISIM_Q_200 or ISIM_Q_500");
+  if (tap->q_ppm > 1000000u) return tfail("q_ppm is above 1000000");
+  if (tap->max_traces > (1ull << 32)) return tfail("max_traces is above 2^32");
+  if (tap->cap_spans > (1ull << 40)) return tfail("cap_spans is above 2^40");
+  if (!tap->d_off || !tap->d_info || (tap->max_traces && !tap->d_ids) || (tap->cap_spans && !tap->d_spans))
+    return tfail("null tap buffer");
+  if (aligned && ((((uintptr_t)tap->d_ids | (uintptr_t)tap->d_off | (uintptr_t)tap->d_info |
+                    (uintptr_t)tap->d_wait_table) & 7u) || ((uintptr_t)tap->d_spans & 15u)))
+    return tfail("the tap's buffers must be 8-byte aligned, d_spans 16-byte aligned");
+  return ISIM_OK;
+}
+
+// the load of a batch, checked as isim_serve_des_device (lp null) or isim_serve_des_profile_device checks it
+int des_load_check(isim_handler *h, const isim_des_params *dp, const isim_load_profile *lp, uint64_t n_traces,
+                   isim::lp::Compiled &c, DesLoad &load) {
+  if (lp) {
+    if (dp->reserved != 0) return fail(ISIM_EINVAL, "isim_des_params.reserved must be 0");
+    return profile_des_check(h, lp, dp->flags, n_traces, c, load);
+  }
+  if (dp->mean_interarrival_ns == 0 || dp->mean_interarrival_ns > (1ull << 34))
+    return fail(ISIM_EINVAL, "mean_interarrival_ns must be in [1, 2^34]");
+  if (dp->reserved != 0 || (dp->flags & ~ISIM_DES_FLAG_WIDE) != 0)
+    return fail(ISIM_EINVAL, "isim_des_params.flags must be 0 or ISIM_DES_FLAG_WIDE, reserved 0");
+  if (n_traces > (1ull << 31)) return fail(ISIM_EINVAL, "n_traces above 2^31 per DES batch");
+  load = DesLoad{dp->mean_interarrival_ns, nullptr, 0, dp->flags};
+  return ISIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int isim_des_wait_table_words(const isim_handler *h, uint64_t *words) {
+  if (!h || !words) return tfail("null argument");
+  *words = ((uint64_t)h->prog.n_services + 1) * ISIM_DW_ROW_WORDS;
+  return ISIM_OK;
+}
+
+int isim_des_wait_merge(const isim_handler *h, uint64_t *dst, const uint64_t *src) {
+  if (!h || !dst || !src) return tfail("null argument");
+  const uint64_t ns = (uint64_t)h->prog.n_services;
+  for (uint64_t r = 0; r <= ns; ++r)
+    for (uint32_t w = 0; w < ISIM_DW_ROW_WORDS; ++w) {
+      uint64_t &d = dst[r * ISIM_DW_ROW_WORDS + w];
+      const uint64_t v = src[r * ISIM_DW_ROW_WORDS + w];
+      d = r < ns && w == ISIM_DW_MAX_WAIT ? std::max(d, v) : d + v;
+    }
+  return ISIM_OK;
+}
+
+int isim_serve_des_spans_device(isim_handler *h, const isim_des_params *dp, const isim_load_profile *lp,
+                                uint64_t trace_begin, uint64_t n_traces, isim_trace_rec *d_records, uint64_t *d_stats,
+                                uint64_t *d_des_table, void *d_workspace, uint64_t workspace_bytes,
+                                const isim_des_tap *tap, void *hip_stream) {
+  if (!h || !dp) return fail(ISIM_EINVAL, "null argument");
+  if (!tap)  // the existing path, whatever it checks
+    return lp ? isim_serve_des_profile_device(h, lp, dp->flags, trace_begin, n_traces, d_records, d_stats,
+                                              d_des_table, d_workspace, workspace_bytes, hip_stream)
+              : isim_serve_des_device(h, dp, trace_begin, n_traces, d_records, d_stats, d_des_table, d_workspace,
+                                      workspace_bytes, hip_stream);
+  // the checks of those two calls, then the tap's, all before any HIP call
+  isim::lp::Compiled c;
+  DesLoad load{};
+  if (const int rc = des_load_check(h, dp, lp, n_traces, c, load)) return rc;
+  if (!d_stats || !d_des_table) return fail(ISIM_EINVAL, "null argument");
+  if (const int rc = des_tap_check(h, tap, d_records || !n_traces, true)) return rc;
+  if (((uintptr_t)d_stats & 7u) || ((uintptr_t)d_des_table & 7u) || ((uintptr_t)d_workspace & 7u) ||
+      ((uintptr_t)d_records & 15u))
+    return fail(ISIM_EINVAL, "d_stats, d_des_table and d_workspace must be 8-byte, d_records 16-byte aligned");
+  if (n_traces && (!d_workspace || workspace_bytes < isim::des_items_workspace_bytes(n_traces)))
+    return fail(ISIM_EINVAL, "DES workspace smaller than isim_des_workspace_bytes()");
+  if (n_traces == 0)  // no batch: an empty list (spans.hip's scan of nothing) with no match
+    return isim::des_items_tap_none(*tap, hip_stream) ? fail(ISIM_EHIP, "DES spans: kernel launch failed") : ISIM_OK;
+  load.tap = tap;
+  return serve_des_device(h, load, trace_begin, n_traces, d_records, d_stats, d_des_table, d_workspace,
+                          workspace_bytes, hip_stream);
+}
+
+int isim_serve_des_spans(isim_handler *h, int device, const isim_des_params *dp, const isim_load_profile *lp,
+                         uint64_t trace_begin, uint64_t n_traces, isim_trace_rec *h_records, uint64_t *h_stats,
+                         uint64_t *h_des_table, const isim_des_tap *tap) {
+  if (!h || !dp) return fail(ISIM_EINVAL, "null argument");
+  if (!tap)
+    return lp ? isim_serve_des_profile(h, device, lp, trace_begin, n_traces, h_records, h_stats, h_des_table)
+              : isim_serve_des(h, device, dp, trace_begin, n_traces, h_records, h_stats, h_des_table);
+  if (const int rc = des_tap_check(h, tap, true, false)) return rc;
+  {
+    isim::lp::Compiled c;
+    DesLoad load{};
+    if (const int rc = des_load_check(h, dp, lp, n_traces, c, load)) return rc;
+  }
+  uint64_t tab_words = 0;
+  (void)isim_des_wait_table_words(h, &tab_words);
+  const uint64_t n_ids = std::min<uint64_t>(tap->max_traces, n_traces);  // the list is no longer than the batch
+  isim_des_tap dt = *tap;
+  dt.max_traces = n_ids;
+  int rc = ISIM_OK;
+  {
+    isim::HostStage stage(device);  // the tap's buffers on `device`; the batch itself runs on serve_des_host's stream
+    dt.d_ids = (uint64_t *)stage.alloc(n_ids * 8);
+    dt.d_off = (uint64_t *)stage.alloc((n_ids + 1) * 8);
+    dt.d_spans = (isim_des_span *)stage.alloc(tap->cap_spans * sizeof(isim_des_span));
+    dt.d_info = (uint64_t *)stage.alloc(ISIM_DES_SPAN_INFO_WORDS * 8);
+    dt.d_wait_table = tap->d_wait_table ? (uint64_t *)stage.upload(tap->d_wait_table, tab_words * 8) : nullptr;
+    if (stage.rc() != ISIM_OK) return stage.rc();
+    if (hipStreamSynchronize(stage.stream()) != hipSuccess) return fail(ISIM_EHIP, "DES spans: table upload failed");
+    rc = serve_des_host(h, device, dp->flags, n_traces, h_records, h_stats, h_des_table,
+                        [&](uint32_t flags, isim_trace_rec *d_rec, uint64_t *d_stats, uint64_t *d_tab, void *d_ws,
+                            uint64_t ws_bytes, hipStream_t s) {
+                          isim_des_params p = *dp;
+                          p.flags = flags;
+                          return isim_serve_des_spans_device(h, &p, lp, trace_begin, n_traces, d_rec, d_stats, d_tab,
+                                                             d_ws, ws_bytes, &dt, s);
+                        },
+                        true);
+    if (rc != ISIM_OK) return rc;
+    uint64_t info[ISIM_DES_SPAN_INFO_WORDS] = {};
+    if ((rc = stage.download(info, dt.d_info, sizeof info)) != ISIM_OK) return rc;
+    std::memcpy(tap->d_info, info, sizeof info);
+    const uint64_t listed = info[ISIM_SPAN_N_IDS], written = info[ISIM_SPAN_WRITTEN];
+    if ((rc = stage.download(tap->d_off, dt.d_off, (listed + 1) * 8)) != ISIM_OK) return rc;
+    if ((rc = stage.download(tap->d_ids, dt.d_ids, listed * 8)) != ISIM_OK) return rc;
+    if ((rc = stage.download(tap->d_spans, dt.d_spans, tap->d_off[written] * sizeof(isim_des_span))) != ISIM_OK) return rc;
+    if (dt.d_wait_table) rc = stage.download(tap->d_wait_table, dt.d_wait_table, tab_words * 8);
+  }
+  return rc;
 }
 
 }  // extern "C"

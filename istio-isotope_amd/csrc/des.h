@@ -267,9 +267,16 @@ struct DesItemsLaunch {
   void *pool;  // hipMemPool_t
   DesItemsReport *report;  // filled when the batch ends (null: none)
   const lp::DeviceProfile *profile;  // the arrivals follow it (null: the constant mean_ns)
+  // the span tap (null: none): the chosen traces' invocations, written after the records while
+  // the item arrays are alive; the slot-to-callee table on the device, the entry service, the services
+  const isim_des_tap *tap;
+  const uint32_t *d_slot_callee;
+  uint32_t entry_service, n_services;
 };
 uint64_t des_items_workspace_bytes(uint64_t n);
 int des_items_launch(const DesItemsLaunch &L, void *stream, std::string &err);
+// a tap's outputs when there is no batch to tap: an empty list (d_off[0] = 0, d_info of no trace); 0 or 1
+int des_items_tap_none(const isim_des_tap &tap, void *stream);
 
 // -ln(w / 2^24), w = (u >> 8) + 1, in Q24 fixed point:
 // log1p(i/256) table, 16-bit linear interpolation.  Shared by host and device.

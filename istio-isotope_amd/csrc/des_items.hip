@@ -56,6 +56,7 @@
 #include "des_layout.h"
 #include "kernel_abi.h"
 #include "load_profile.h"
+#include "spans.h"
 #include "tree_walk.h"
 
 namespace isim {
@@ -1400,6 +1401,131 @@ __global__ void k_flag_retry(unsigned long long *stats, const uint32_t *ovf) {
   else if (ovf[0] || ovf[1]) atomicAdd(stats + ISIM_ST_DES_RETRY, 1ull);
 }
 
+// ---- 6. the span tap: the executed invocations of chosen
+// traces out of the live item arrays.  The chosen ids are ascending; a trace's
+// span count is its item count
+struct TapK {
+  const uint64_t *ids;          // [n_sel]
+  const uint64_t *off;          // [n_sel + 1]: the exclusive scan of the counts
+  const uint64_t *info;         // ISIM_SPAN_WRITTEN: the traces that fit (a prefix of the list)
+  const uint32_t *inv;          // trace-order item -> position-major item
+  const uint32_t *slot_callee;
+  isim_des_span *spans;
+  unsigned long long *wait;     // the wait table (null: none)
+  uint32_t entry, n_services, wide;
+};
+
+__global__ void __launch_bounds__(kT) k_tap_count(K k, const uint64_t *ids, uint64_t n_sel, uint32_t *cnt,
+                                                  uint64_t *info, uint64_t matches) {
+  if (gid() == 0) info[ISIM_DES_SPAN_MATCHES] = matches;
+  for (uint64_t i = gid(); i < n_sel; i += nthreads()) {
+    const uint64_t t = ids[i] - k.trace_begin;
+    cnt[i] = (uint32_t)(k.tend[t] - item_off(k, t));
+  }
+}
+
+// One span per lane: span g belongs to the list entry i with off[i] <= g <
+// off[i + 1] (a binary search of the small offset array), its hop is g - off[i],
+// its item inv[first item of the trace + hop].  The gathers are scattered; a
+// wave stores 64 consecutive 64-byte spans, each as four 16-byte stores.  Table:
+// one set of atomics per span into its service's row; the entries (one per
+// trace, all of one service) and the header are summed over the wave first
+__global__ void __launch_bounds__(kT) k_tap_emit(K k, TapK q) {
+  const uint64_t written = q.info[ISIM_SPAN_WRITTEN];
+  const uint64_t total = q.off[written];
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint64_t g0 = gid() - lane; g0 < total; g0 += nthreads()) {  // whole waves stay in the loop
+    const uint64_t g = g0 + lane;
+    const bool on = g < total;
+    bool entry = false, st = false;
+    uint64_t w = 0, dur = 0;
+    if (on) {
+      uint64_t lo = 0, hi = written;  // off[lo] <= g < off[hi]
+      while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (q.off[mid] <= g) lo = mid;
+        else hi = mid;
+      }
+      const uint32_t hop = (uint32_t)(g - q.off[lo]);
+      const uint64_t trace = q.ids[lo], t = trace - k.trace_begin;
+      const uint32_t j = q.inv[item_off(k, t) + hop];
+      const uint32_t v = k.ipos[j], par = k.ipar[j];
+      const uint64_t a = k.IA[j], S = k.IS[j], F = k.IF[j];
+      entry = par == kNone;
+      st = k.iown[j] != 0;
+      const TreeExt x = tw::load_ext(k.ext, v);
+      uint32_t slot, fl;
+      if (q.wide) {
+        const tw::NodeW4 nd = GNodesW{(const uint4 *)k.nodes}.load(v);
+        slot = nd.slot();
+        fl = nd.flags();
+      } else {
+        const tw::NodeW nd = GNodes{k.nodes}.load(v);
+        slot = nd.slot();
+        fl = nd.flags();
+      }
+      const uint32_t svc = entry ? q.entry : q.slot_callee[slot];
+      const bool leaf = (fl & TF_LEAF) != 0;
+      const uint32_t status =
+          k.modeb ? spans::span_status<true>(st, leaf, (uint32_t)trace, (uint32_t)(trace >> 32), hop, fl, x.thr, k.k0, k.k1)
+                  : spans::span_status<false>(st, leaf, (uint32_t)trace, (uint32_t)(trace >> 32), hop, fl, x.thr, k.k0,
+                                              k.k1);
+      const uint64_t H = entry ? 0ull : (uint64_t)x.H;
+      uint4 *o = (uint4 *)(q.spans + g);
+      o[0] = uint4{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)S, (uint32_t)(S >> 32)};
+      o[1] = uint4{(uint32_t)F, (uint32_t)(F >> 32), (uint32_t)H, (uint32_t)(H >> 32)};
+      o[2] = uint4{hop, entry ? kNone : k.ihop[par], v, entry ? kNone : slot};
+      o[3] = uint4{svc, status, (uint32_t)k.irep[j], 0u};
+      w = S - a;
+      dur = F - a;
+      if (q.wait && !entry && svc < q.n_services) {
+        unsigned long long *row = q.wait + (uint64_t)svc * ISIM_DW_ROW_WORDS;
+        atomicAdd(row + ISIM_DW_INVOCATIONS, 1ull);
+        if (w) {
+          atomicAdd(row + ISIM_DW_WAITED, 1ull);
+          atomicAdd(row + ISIM_DW_SUM_WAIT, (unsigned long long)w);
+          atomicMax(row + ISIM_DW_MAX_WAIT, (unsigned long long)w);
+        }
+        atomicAdd(row + ISIM_DW_SUM_DURATION, (unsigned long long)dur);
+        if (st) atomicAdd(row + ISIM_DW_RESP_500, 1ull);
+      }
+    }
+    if (!q.wait) continue;
+    // the entries and the header: one set of atomics per wave
+    const unsigned long long n_sp = (unsigned long long)__popcll(__ballot(on));
+    const unsigned long long em = __ballot(entry);
+    if (!em) {
+      if (lane == 0) atomicAdd(q.wait + (uint64_t)q.n_services * ISIM_DW_ROW_WORDS + ISIM_DW_H_SPANS, n_sp);
+      continue;
+    }
+    unsigned long long sw = entry ? w : 0ull, mw = sw, sd = entry ? dur : 0ull;
+    for (uint32_t d = 32; d > 0; d >>= 1) {
+      sw += __shfl_xor(sw, d, 64);
+      sd += __shfl_xor(sd, d, 64);
+      const unsigned long long y = __shfl_xor(mw, d, 64);
+      mw = y > mw ? y : mw;
+    }
+    const unsigned long long n_e = (unsigned long long)__popcll(em), n_w = (unsigned long long)__popcll(__ballot(entry && w)),
+                             n_5 = (unsigned long long)__popcll(__ballot(entry && st));
+    if (lane == 0) {
+      unsigned long long *row = q.wait + (uint64_t)q.entry * ISIM_DW_ROW_WORDS;
+      unsigned long long *hd = q.wait + (uint64_t)q.n_services * ISIM_DW_ROW_WORDS;
+      atomicAdd(row + ISIM_DW_INVOCATIONS, n_e);
+      if (n_w) {
+        atomicAdd(row + ISIM_DW_WAITED, n_w);
+        atomicAdd(row + ISIM_DW_SUM_WAIT, sw);
+        atomicMax(row + ISIM_DW_MAX_WAIT, mw);
+      }
+      atomicAdd(row + ISIM_DW_SUM_DURATION, sd);
+      if (n_5) atomicAdd(row + ISIM_DW_RESP_500, n_5);
+      atomicAdd(hd + ISIM_DW_H_TRACES, n_e);
+      atomicAdd(hd + ISIM_DW_H_SPANS, n_sp);
+      atomicAdd(hd + ISIM_DW_H_SUM_LATENCY, sd);
+      if (sw) atomicAdd(hd + ISIM_DW_H_SUM_WAIT, sw);
+    }
+  }
+}
+
 }  // namespace dit
 
 namespace {
@@ -1955,12 +2081,83 @@ struct Batch {
     if (hipGetLastError() != hipSuccess) return fail("kernel launch");
     // a look-back that gave up (k_qscan) fails the batch loudly: nothing was
     // accumulated (k_final) and the call returns the error
-    uint32_t fault = 0;
-    if (hipMemcpyAsync(&fault, B.ovf + 2, 4, hipMemcpyDeviceToHost, s) != hipSuccess || sync_s() != hipSuccess)
+    uint32_t ovf[3] = {0, 0, 0};  // key overflow, no fixed point (k_flag_retry counted them), look-back fault
+    if (hipMemcpyAsync(ovf, B.ovf, 12, hipMemcpyDeviceToHost, s) != hipSuccess || sync_s() != hipSuccess)
       return fail("fault read-back");
-    if (fault)
+    if (ovf[2]) {
+      if (L.tap) (void)tap_none();
       return fail("a queue scan's look-back gave up waiting for an earlier tile (k_qscan): the batch was not "
                   "accumulated");
+    }
+    if (!L.tap) return 0;
+    return ovf[0] || ovf[1] ? tap_none() : tap();
+  }
+
+  // 6. the span tap.  A batch that is not accumulated (a fault, ISIM_ST_DES_RETRY) has no trace chosen:
+  // d_off[0] = 0, d_info of an empty list, nothing else
+  int tap_none() { return des_items_tap_none(*L.tap, s) ? fail("tap launch") : 0; }
+
+  // The chosen traces (the threshold given, or this batch's order statistic: §13's select and one word read
+  // back), their ids by the selection of spans.hip, the counts scanned by its scan, the spans and the table
+  int tap() {
+    const isim_des_tap &tp = *L.tap;
+    const uint64_t bound = std::min<uint64_t>(tp.max_traces, n);  // no more traces than the batch has
+    uint64_t qws_bytes = 0;
+    if (isim_quantiles_workspace_bytes(1, &qws_bytes) != ISIM_OK) return fail("tap workspace");
+    struct {
+      uint64_t *qout, *sel, *tile;
+      uint32_t *cnt;
+      void *qws;
+    } W{};
+    auto layout = [&](Arena &a) {
+      W.qout = a.take<uint64_t>(ISIM_Q_OUT_WORDS(1));
+      W.sel = a.take<uint64_t>(2);
+      W.tile = a.take<uint64_t>(spans::tiles_of(n) + 1);  // the selection's tiles over n, then the scan's over the list
+      W.cnt = a.take<uint32_t>(bound);
+      W.qws = a.take<char>(qws_bytes);
+    };
+    Arena sizing;
+    layout(sizing);
+    PoolBuf mem{nullptr, s};
+    if (!pool_alloc(mem, sizing.bytes())) return fail("tap allocation");
+    Arena carving(mem.p);
+    layout(carving);
+    uint64_t thr = tp.min_latency_ns;
+    if (tp.q_ppm) {
+      const uint32_t q = tp.q_ppm;
+      if (isim_latency_quantiles_device(k.records, n, &q, 1, W.qout, W.qws, qws_bytes, s) != ISIM_OK)
+        return fail("tap: the percentile select was refused");
+      if (hipMemcpyAsync(&thr, W.qout + (uint64_t)tp.cls * 2 + 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+          sync_s() != hipSuccess)
+        return fail("tap threshold read-back");
+    }
+    if (spans::select_launch(k.records, n, L.trace_begin, thr, tp.cls, tp.max_traces, tp.d_ids, W.sel, W.tile, s) !=
+        ISIM_OK)
+      return fail("tap selection launch");
+    uint64_t sel[2] = {0, 0};  // matches, written
+    if (hipMemcpyAsync(sel, W.sel, 16, hipMemcpyDeviceToHost, s) != hipSuccess || sync_s() != hipSuccess)
+      return fail("tap selection read-back");
+    const uint64_t n_sel = sel[1];
+    hipLaunchKernelGGL(k_tap_count, dim3(grid_for(n_sel)), dim3(kT), 0, s, k, (const uint64_t *)tp.d_ids, n_sel, W.cnt,
+                       tp.d_info, sel[0]);
+    if (spans::scan_launch(W.cnt, n_sel, W.tile, tp.d_off, tp.cap_spans, tp.d_info, s) != ISIM_OK)
+      return fail("tap scan launch");
+    if (n_sel && tp.cap_spans) {
+      TapK q{};
+      q.ids = tp.d_ids;
+      q.off = tp.d_off;
+      q.info = tp.d_info;
+      q.inv = B.inv;
+      q.slot_callee = L.d_slot_callee;
+      q.spans = tp.d_spans;
+      q.wait = (unsigned long long *)tp.d_wait_table;
+      q.entry = L.entry_service;
+      q.n_services = L.n_services;
+      q.wide = L.tree_wide;
+      hipLaunchKernelGGL(k_tap_emit, dim3(grid_for(std::min<uint64_t>(tp.cap_spans, M))), dim3(kT), 0, s, k, q);
+    }
+    if (hipGetLastError() != hipSuccess) return fail("tap launch");
+    // the pool takes the buffers back in stream order, after the kernels above
     return 0;
   }
 };
@@ -1972,6 +2169,14 @@ uint64_t des_items_workspace_bytes(uint64_t n) {
   ItemTraceBufs t;
   des_items_trace_layout(sizing, t, n, scan_u64_bytes(n));
   return sizing.bytes();
+}
+
+int des_items_tap_none(const isim_des_tap &tap, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (spans::scan_launch(nullptr, 0, nullptr, tap.d_off, tap.cap_spans, tap.d_info, s) != ISIM_OK) return 1;
+  hipLaunchKernelGGL(dit::k_tap_count, dim3(1), dim3(dit::kT), 0, s, dit::K{}, (const uint64_t *)nullptr, 0ull,
+                     (uint32_t *)nullptr, tap.d_info, 0ull);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 int des_items_launch(const DesItemsLaunch &L, void *stream, std::string &err) {

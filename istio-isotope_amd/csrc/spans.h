@@ -180,6 +180,10 @@ int device_tables(const HandlerView &v, DevTables &out);  // of the current devi
 // the launches of one checked call; ISIM_OK or ISIM_EHIP (message set)
 int spans_launch(const isim_handler *h, const uint64_t *d_ids, uint64_t n_ids, uint64_t *d_off, isim_span *d_spans,
                  uint64_t cap_spans, uint64_t *d_info, void *d_workspace, void *stream);
+// the scan step of spans_launch alone (the DES tap, des_items.hip, shares it): d_cnt[n] -> d_off[n + 1], its
+// exclusive scan, and d_info's four words under cap_spans; d_tile: tiles_of(n) + 1 words; n 0 writes d_off[0] = 0
+int scan_launch(const uint32_t *d_cnt, uint64_t n, uint64_t *d_tile, uint64_t *d_off, uint64_t cap_spans,
+                uint64_t *d_info, void *stream);
 int select_launch(const isim_trace_rec *d_records, uint64_t n, uint64_t trace_begin, uint64_t min_latency,
                   uint32_t cls, uint64_t max_ids, uint64_t *d_ids, uint64_t *d_info, void *d_workspace, void *stream);
 

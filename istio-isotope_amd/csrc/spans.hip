@@ -364,6 +364,22 @@ int device_tables(const HandlerView &v, DevTables &out) {
   return ISIM_OK;
 }
 
+int scan_launch(const uint32_t *d_cnt, uint64_t n, uint64_t *d_tile, uint64_t *d_off, uint64_t cap_spans,
+                uint64_t *d_info, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {  // d_off[0] = 0 and info: the scan of no tiles, with d_off[0] as its total word
+    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, d_off, 0ull, d_off, d_info, 0ull);
+  } else {
+    const uint32_t tiles = (uint32_t)tiles_of(n);
+    hipLaunchKernelGGL(k_tile_sums, dim3(tiles), dim3(kT), 0, s, d_cnt, n, d_tile);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, d_tile, (uint64_t)tiles, d_off + n, d_info, n);
+    hipLaunchKernelGGL(k_offsets, dim3(tiles), dim3(kT), 0, s, d_cnt, n, (const uint64_t *)d_tile, d_off, cap_spans,
+                       d_info);
+  }
+  ISIM_HIPCHK(hipGetLastError());
+  return ISIM_OK;
+}
+
 int spans_launch(const isim_handler *h, const uint64_t *d_ids, uint64_t n_ids, uint64_t *d_off, isim_span *d_spans,
                  uint64_t cap_spans, uint64_t *d_info, void *d_workspace, void *stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -371,11 +387,7 @@ int spans_launch(const isim_handler *h, const uint64_t *d_ids, uint64_t n_ids, u
   const Program &p = *v.prog;
   const SpanWs ws = span_ws(p, n_ids);
   char *wsp = (char *)d_workspace;
-  if (n_ids == 0) {  // d_off[0] = 0 and info: the scan of no tiles, with d_off[0] as its total word
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, d_off, 0ull, d_off, d_info, 0ull);
-    ISIM_HIPCHK(hipGetLastError());
-    return ISIM_OK;
-  }
+  if (n_ids == 0) return scan_launch(nullptr, 0, nullptr, d_off, cap_spans, d_info, stream);
   DevTables t;
   if (const int rc = device_tables(v, t)) return rc;
   unsigned long long *work = (unsigned long long *)(wsp + ws.off_work);
@@ -397,13 +409,10 @@ int spans_launch(const isim_handler *h, const uint64_t *d_ids, uint64_t n_ids, u
   uint64_t *tile = (uint64_t *)(wsp + ws.off_tile);
   const Frames fr = frames_of(p.tree_frames);
   const bool mb = v.params->error_mode == ISIM_MODE_B;
-  const uint32_t blocks = walk_blocks(n_ids), tiles = (uint32_t)tiles_of(n_ids);
+  const uint32_t blocks = walk_blocks(n_ids);
   hipLaunchKernelGGL(k_zero_work, dim3(1), dim3(64), 0, s, work);
   hipLaunchKernelGGL(walk_kernel(fr, p.tree_t64, mb, p.tree_wide, false), dim3(blocks), dim3(kT), 0, s, k, work);
-  hipLaunchKernelGGL(k_tile_sums, dim3(tiles), dim3(kT), 0, s, (const uint32_t *)k.cnt, n_ids, tile);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, tile, (uint64_t)tiles, d_off + n_ids, d_info, n_ids);
-  hipLaunchKernelGGL(k_offsets, dim3(tiles), dim3(kT), 0, s, (const uint32_t *)k.cnt, n_ids, (const uint64_t *)tile,
-                     d_off, cap_spans, d_info);
+  if (const int rc = scan_launch(k.cnt, n_ids, tile, d_off, cap_spans, d_info, stream)) return rc;
   hipLaunchKernelGGL(walk_kernel(fr, p.tree_t64, mb, p.tree_wide, true), dim3(blocks), dim3(kT), 0, s, k, work + 1);
   ISIM_HIPCHK(hipGetLastError());
   return ISIM_OK;

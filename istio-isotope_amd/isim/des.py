@@ -92,6 +92,51 @@ class DesHandler:
             self.handler._h, C.byref(p), trace_begin, n_traces, d_records or None, d_stats, d_table,
             d_workspace, workspace_bytes, stream or None))
 
+    def _load_args(self, wide: bool):
+        """(isim_des_params, isim_load_profile or None) of isim_serve_des_spans*."""
+        mean = self.params.mean_interarrival_ns if self.profile is None else 0
+        p = native.DesParams(mean, native.DES_FLAG_WIDE if wide else 0, 0)
+        return p, (self.profile.c if self.profile is not None else None)
+
+    def serve_spans_device(self, trace_begin: int, n_traces: int, d_records: int, d_stats: int, d_table: int,
+                           d_workspace: int, workspace_bytes: int, tap=None, stream: int = 0,
+                           wide: bool = False) -> None:
+        """isim_serve_des_spans_device: the batch of serve_device, and after it the spans of the traces `tap`
+        (a native.DesTap over device addresses, isim.des_spans.make_tap) chooses.  tap None: serve_device."""
+        p, lp = self._load_args(wide)
+        native.check(native.load().isim_serve_des_spans_device(
+            self.handler._h, C.byref(p), lp, trace_begin, n_traces, d_records or None, d_stats, d_table,
+            d_workspace, workspace_bytes, C.byref(tap) if tap is not None else None, stream or None))
+
+    def serve_spans(self, trace_begin: int, n_traces: int, q_ppm: int = 999000, min_latency_ns: int = None,
+                    cls: int = native.Q_ALL, max_traces: int = 64, cap_spans: int = 2 ** 20, wide: bool = False,
+                    device: int = 0, wait_table=None):
+        """Synchronous: (records, stats, DES table, [DesTrace], DesWaitTable) of one batch.  The traces: the
+        records at or above the batch's q_ppm order statistic (p99.9) in class cls, or at or above
+        min_latency_ns when that is given; ids ascending, the first max_traces whose spans fit cap_spans.
+        wait_table: a DesWaitTable to add into (a new one otherwise).  Item engine only."""
+        from .des_spans import DES_SPAN_DTYPE, DesTrace, DesWaitTable, make_tap
+        from .sim import REC_DTYPE as _REC
+        names = [s["name"] for s in self.handler.graph.canonical()["services"]]
+        waits = wait_table if wait_table is not None else DesWaitTable(self.handler, names=names)
+        n_ids = min(int(max_traces), int(n_traces))
+        ids, off = np.zeros(max(1, n_ids), np.uint64), np.zeros(n_ids + 1, np.uint64)
+        spans = np.zeros(max(1, int(cap_spans)), DES_SPAN_DTYPE)
+        info = np.zeros(native.DES_SPAN_INFO_WORDS, np.uint64)
+        tap = make_tap(0 if min_latency_ns is None else min_latency_ns, q_ppm if min_latency_ns is None else 0, cls,
+                       max_traces, cap_spans, ids.ctypes.data, off.ctypes.data, spans.ctypes.data, info.ctypes.data,
+                       waits.table.ctypes.data)
+        stats, table = self.handler.new_stats(), self.new_table()
+        recs = np.zeros(n_traces, _REC)
+        p, lp = self._load_args(wide)
+        native.check(native.load().isim_serve_des_spans(
+            self.handler._h, device, C.byref(p), lp, trace_begin, n_traces, recs.ctypes.data if n_traces else None,
+            stats.ctypes.data, table.ctypes.data, C.byref(tap)))
+        written = int(info[native.SPAN_WRITTEN])
+        traces = [DesTrace(ids[i], spans[int(off[i]):int(off[i + 1])].copy(), names) for i in range(written)]
+        self.last_tap_info = info
+        return recs, stats, table, traces, waits
+
     def arrivals(self, trace_begin: int, n_traces: int, device: int = 0) -> np.ndarray:
         """The arrival times (u64 ns since batch start) `serve` uses for these traces."""
         if self.profile is not None:

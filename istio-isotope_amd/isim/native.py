@@ -77,6 +77,12 @@ SPAN_CRITICAL = 4
 CP_INVOCATIONS, CP_SUM_DURATION, CP_CRITICAL, CP_SELF_NS, CP_HOP_NS, CP_CRITICAL_500 = range(6)
 CP_ROW_WORDS = 6
 CP_H_TRACES, CP_H_SPANS, CP_H_CRITICAL, CP_H_SUM_LATENCY, CP_H_REFUSED = range(5)
+# isim_serve_des_spans*: the fifth info word, the words of a wait-table row and of its header (isim.h ISIM_DW_*)
+DES_SPAN_MATCHES = 4
+DES_SPAN_INFO_WORDS = 5
+DW_INVOCATIONS, DW_WAITED, DW_SUM_WAIT, DW_MAX_WAIT, DW_SUM_DURATION, DW_RESP_500 = range(6)
+DW_ROW_WORDS = 6
+DW_H_TRACES, DW_H_SPANS, DW_H_SUM_LATENCY, DW_H_SUM_WAIT = range(4)
 
 
 def SK_BINS(s: int) -> int:
@@ -160,6 +166,20 @@ class MultiId(C.Structure):
 
 class DesBatchStats(C.Structure):
     _fields_ = [("passes", C.c_uint32), ("syncs", C.c_uint32), ("items", C.c_uint64)]
+
+
+class DesSpan(C.Structure):
+    _fields_ = [("arrival_ns", C.c_uint64), ("start_ns", C.c_uint64), ("finish_ns", C.c_uint64),
+                ("hop_ns", C.c_uint64), ("hop", C.c_uint32), ("caller_hop", C.c_uint32), ("position", C.c_uint32),
+                ("slot", C.c_uint32), ("service", C.c_uint32), ("status", C.c_uint32), ("replica", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class DesTap(C.Structure):
+    _fields_ = [("min_latency_ns", C.c_uint64), ("q_ppm", C.c_uint32), ("cls", C.c_uint32),
+                ("max_traces", C.c_uint64), ("cap_spans", C.c_uint64), ("d_ids", C.c_void_p), ("d_off", C.c_void_p),
+                ("d_spans", C.c_void_p), ("d_info", C.c_void_p), ("d_wait_table", C.c_void_p),
+                ("reserved", C.c_uint64 * 2)]
 
 
 class DesInfo(C.Structure):
@@ -273,6 +293,12 @@ SIGNATURES = {
     "isim_critical_path_device": (C.c_int, [_VP, _VP, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP]),
     "isim_critical_path_host": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP]),
     "isim_critical_path": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, _VP, _VP]),
+    "isim_des_wait_table_words": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
+    "isim_des_wait_merge": (C.c_int, [_VP, _VP, _VP]),
+    "isim_serve_des_spans_device": (C.c_int, [_VP, C.POINTER(DesParams), C.POINTER(LoadProfile), C.c_uint64,
+                                              C.c_uint64, _VP, _VP, _VP, _VP, C.c_uint64, C.POINTER(DesTap), _VP]),
+    "isim_serve_des_spans": (C.c_int, [_VP, C.c_int, C.POINTER(DesParams), C.POINTER(LoadProfile), C.c_uint64,
+                                       C.c_uint64, _VP, _VP, _VP, C.POINTER(DesTap)]),
 }
 
 _lib = None
