@@ -411,6 +411,64 @@ func (h *Handler) DesWaitMerge(dst, src []uint64) error {
 	return lastErr(C.isim_des_wait_merge(h.h, u64ptr(dst), u64ptr(src)))
 }
 
+// The DES critical-path table (DESIGN §22): (services + 1) rows of DcpRowWords
+// words; row s the words below, the last row the header.  Tables merge by
+// addition (DesCriticalPathMerge).
+const (
+	DcpInvocations    = C.ISIM_DCP_INVOCATIONS
+	DcpSumDuration    = C.ISIM_DCP_SUM_DURATION
+	DcpCritical       = C.ISIM_DCP_CRITICAL
+	DcpWaitNs         = C.ISIM_DCP_WAIT_NS
+	DcpSelfNs         = C.ISIM_DCP_SELF_NS
+	DcpHopNs          = C.ISIM_DCP_HOP_NS
+	DcpCritical500    = C.ISIM_DCP_CRITICAL_500
+	DcpCriticalWaited = C.ISIM_DCP_CRITICAL_WAITED
+	DcpRowWords       = C.ISIM_DCP_ROW_WORDS
+	DcpHTraces        = C.ISIM_DCP_H_TRACES
+	DcpHSpans         = C.ISIM_DCP_H_SPANS
+	DcpHCritical      = C.ISIM_DCP_H_CRITICAL
+	DcpHSumLatency    = C.ISIM_DCP_H_SUM_LATENCY
+	DcpHRefused       = C.ISIM_DCP_H_REFUSED
+)
+
+// DesCriticalPath folds the traces ServeDesSpans returned on GPU `device`
+// (isim_des_critical_path): it ORs SpanCritical into the status of the spans on
+// each trace's critical path and returns the table and, per trace, the queue
+// wait on its critical path (math.MaxUint64 for a refused trace).
+func (h *Handler) DesCriticalPath(device int, traces [][]DesSpan) ([]uint64, []uint64, error) {
+	var words C.uint64_t
+	if err := lastErr(C.isim_des_critical_path_table_words(h.h, &words)); err != nil {
+		return nil, nil, err
+	}
+	off := make([]uint64, len(traces)+1)
+	for i, t := range traces {
+		off[i+1] = off[i] + uint64(len(t))
+	}
+	all := make([]DesSpan, 0, off[len(traces)]+1)
+	for _, t := range traces {
+		all = append(all, t...)
+	}
+	table := make([]uint64, words)
+	wait := make([]uint64, len(traces)+1)
+	var sp *C.isim_des_span
+	if len(all) > 0 {
+		sp = (*C.isim_des_span)(unsafe.Pointer(&all[0]))
+	}
+	rc := C.isim_des_critical_path(C.int(device), h.h, u64ptr(off), C.uint64_t(len(traces)), sp, u64ptr(table), u64ptr(wait))
+	if err := lastErr(rc); err != nil {
+		return nil, nil, err
+	}
+	for i, t := range traces {
+		copy(t, all[off[i]:off[i+1]])
+	}
+	return table, wait[:len(traces)], nil
+}
+
+// DesCriticalPathMerge adds src into dst (isim_des_critical_path_merge).
+func (h *Handler) DesCriticalPathMerge(dst, src []uint64) error {
+	return lastErr(C.isim_des_critical_path_merge(h.h, u64ptr(dst), u64ptr(src)))
+}
+
 // SelectTraces returns the ids begin + i of the records with a latency of at
 // least minLatencyNs in class cls (C.ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500), in
 // ascending i, at most maxIDs of them, and the number of matching records

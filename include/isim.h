@@ -1017,7 +1017,8 @@ typedef struct {
   uint32_t position;     /* as isim_span */
   uint32_t slot;         /* as isim_span; 0xFFFFFFFF for the entry */
   uint32_t service;      /* as isim_span */
-  uint32_t status;       /* as isim_span: bit 0 responded 500, bit 1 its own error draw */
+  uint32_t status;       /* as isim_span: bit 0 responded 500, bit 1 its own error draw; bit 2 (ISIM_SPAN_CRITICAL)
+                          * set by isim_des_critical_path* only */
   uint32_t replica;      /* the replica the §10.1 draw chose; 0 when the service has one */
   uint32_t reserved;     /* 0 */
 } isim_des_span;         /* 64 bytes */
@@ -1096,6 +1097,96 @@ ISIM_API int isim_serve_des_spans(isim_handler *h, int device, const isim_des_pa
                                   const isim_load_profile *lp, uint64_t trace_begin, uint64_t n_traces,
                                   isim_trace_rec *h_records, uint64_t *h_stats, uint64_t *h_des_table,
                                   const isim_des_tap *tap);
+
+/* ---- DES critical path: queue wait, self time and hop cost per service (EXT) ----
+ * The wait table above folds every wait of the tapped traces; it cannot say
+ * which waits mattered: a long queue in a branch of a concurrent step that lost
+ * anyway costs the trace nothing.  This fold marks the critical path of each
+ * trace of isim_des_span records and splits its latency per service into queue
+ * wait, self time and hop cost.
+ *
+ * Per span v: dur(v) = finish_ns - arrival_ns, wait(v) = start_ns - arrival_ns,
+ * run(v) = finish_ns - start_ns.
+ *
+ * Replay.  A caller's script is replayed with the clock starting at the caller's
+ * start_ns.  Its executed children, in hop order, are matched to the call
+ * commands by the call index of their positions, as isim_critical_path matches
+ * them.  A sleep adds max(d, 0).  A sequential call whose child c executed must
+ * satisfy arrival_ns(c) == clock + hop_ns(c) and adds hop_ns(c) + dur(c).  In a
+ * concurrent step every executed member must satisfy that equation at the
+ * step's begin; the clock advances by the largest member value.
+ *
+ * Local winners, critical set: the rules of isim_critical_path with
+ * duration_ns read as dur(c).
+ *
+ * Parts of a critical span: wait(v), hop_ns(v) and self(v) = run(v) - the sum
+ * over v's local-winner children c of (hop_ns(c) + dur(c)).
+ *
+ * Identity.  Per trace the sum over its critical spans of (wait + self + hop_ns)
+ * equals the entry's finish_ns - arrival_ns, the record's latency_ns.
+ *
+ * Refused traces (left untouched, counted in ISIM_DCP_H_REFUSED, by the host
+ * and the device alike): offsets not ascending, past cap_spans or past the
+ * written spans, more than 2^32 - 1 spans; a span with hop != j, a caller_hop
+ * that is not j - 1 or one of its callers (the entry: not the sentinel, or a
+ * hop_ns other than 0), a position or a service out of range, or not
+ * arrival_ns <= start_ns <= finish_ns; a child whose arrival equation fails or
+ * that matches no call command of its caller; a self below 0.
+ *
+ * The table: (n_services + 1) rows of ISIM_DCP_ROW_WORDS u64 words, every word
+ * a sum mod 2^64, so tables merge by plain addition.  Row s < n_services: the
+ * words below.  The last row is the header.  Per table the sum over s of
+ * (WAIT_NS + SELF_NS + HOP_NS) equals the header's ISIM_DCP_H_SUM_LATENCY.
+ * ISIM_SPAN_CRITICAL (bit 2) is ORed into isim_des_span.status of the critical
+ * spans; nothing else in a span is written. */
+#define ISIM_DCP_INVOCATIONS     0   /* every executed invocation of s in the folded traces */
+#define ISIM_DCP_SUM_DURATION    1   /* the sum of their finish_ns - arrival_ns */
+#define ISIM_DCP_CRITICAL        2   /* invocations of s on the path */
+#define ISIM_DCP_WAIT_NS         3   /* the sum of the queue waits of the critical invocations */
+#define ISIM_DCP_SELF_NS         4   /* the sum of their self times */
+#define ISIM_DCP_HOP_NS          5   /* the sum of their hop_ns: the network time of the calls into s */
+#define ISIM_DCP_CRITICAL_500    6   /* critical invocations that responded 500 */
+#define ISIM_DCP_CRITICAL_WAITED 7   /* critical invocations with start_ns > arrival_ns */
+#define ISIM_DCP_ROW_WORDS       8
+/* the header row (row n_services); its last three words are 0 */
+#define ISIM_DCP_H_TRACES      0  /* traces folded */
+#define ISIM_DCP_H_SPANS       1  /* their spans */
+#define ISIM_DCP_H_CRITICAL    2  /* their critical spans */
+#define ISIM_DCP_H_SUM_LATENCY 3  /* the sum of their entries' finish_ns - arrival_ns */
+#define ISIM_DCP_H_REFUSED     4  /* traces refused; left untouched, counted nowhere else */
+
+/* host only, no GPU: (n_services + 1) * ISIM_DCP_ROW_WORDS */
+ISIM_API int isim_des_critical_path_table_words(const isim_handler *h, uint64_t *words);
+/* host only, no GPU: 16 bytes per span of the buffer plus 64 */
+ISIM_API int isim_des_critical_path_workspace_bytes(const isim_handler *h, uint64_t cap_spans, uint64_t *bytes);
+/* host only, no GPU: dst[w] += src[w] over the table's words */
+ISIM_API int isim_des_critical_path_merge(const isim_handler *h, uint64_t *dst, const uint64_t *src);
+/* The fold of the d_info[ISIM_SPAN_WRITTEN] traces that a preceding
+ * isim_serve_des_spans_device with a tap of n_ids = max_traces list entries
+ * wrote to d_off / d_spans, on the current device, asynchronously on
+ * hip_stream.  The number of traces is read on the device (at most n_ids, which
+ * bounds the grid).  ADDS into d_table (the caller zeroes it).  d_trace_wait:
+ * NULL, or u64[n_ids]; entry i gets the sum of wait over the critical spans of
+ * list entry i, UINT64_MAX for a refused trace; entries past the written count
+ * are untouched.  One trace per wave.  No host synchronisation,
+ * graph-capturable from the first call, the workspace may be dirty (calls that
+ * share one must be ordered).  n_ids 0 does nothing.  ISIM_EINVAL, before any
+ * HIP call: a handler isim_serve_des_spans_device refuses with a tap, a null
+ * argument, n_ids above 2^32, cap_spans above 2^40, buffers not 8-byte aligned
+ * (d_spans 16), a workspace below isim_des_critical_path_workspace_bytes(h,
+ * cap_spans). */
+ISIM_API int isim_des_critical_path_device(const isim_handler *h, const uint64_t *d_off, isim_des_span *d_spans,
+                                           uint64_t cap_spans, const uint64_t *d_info, uint64_t n_ids,
+                                           uint64_t *d_table, uint64_t *d_trace_wait, void *d_workspace,
+                                           uint64_t workspace_bytes, void *hip_stream);
+/* host only, no GPU: the same fold on the CPU over the n_written traces at
+ * h_spans[h_off[i] .. h_off[i + 1]); a trace that reaches past h_off[n_written]
+ * is refused.  ADDS into h_table; h_trace_wait NULL or u64[n_written]. */
+ISIM_API int isim_des_critical_path_host(const isim_handler *h, const uint64_t *h_off, uint64_t n_written,
+                                         isim_des_span *h_spans, uint64_t *h_table, uint64_t *h_trace_wait);
+/* Synchronous convenience: host buffers, on GPU `device`. */
+ISIM_API int isim_des_critical_path(int device, const isim_handler *h, const uint64_t *h_off, uint64_t n_written,
+                                    isim_des_span *h_spans, uint64_t *h_table, uint64_t *h_trace_wait);
 
 #ifdef __cplusplus
 }

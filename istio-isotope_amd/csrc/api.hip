@@ -19,6 +19,7 @@
 #include "k8s.h"
 #include "marshal.h"
 #include "des.h"
+#include "des_critical_path.h"
 #include "host_stage.h"
 #include "kernel_abi.h"
 #include "load_profile.h"
@@ -1502,12 +1503,18 @@ namespace {
 
 int tfail(const std::string &msg) { return fail(ISIM_EINVAL, "DES spans: " + msg); }
 
-// every check of a tap that needs no GPU; `aligned`: the five pointers are device buffers
-int des_tap_check(const isim_handler *h, const isim_des_tap *tap, bool have_records, bool aligned) {
+// a handler that has DES spans: its DES runs on the item engine
+int des_items_check(const isim_handler *h) {
   if (const int drc = des_ensure(h)) return drc;
   if (!h->des.items)
     return tfail("this handler's DES runs on the static engine, which keeps no invocations: create the handler "
                  "with ISIM_FLAG_DYNAMIC");
+  return ISIM_OK;
+}
+
+// every check of a tap that needs no GPU; `aligned`: the five pointers are device buffers
+int des_tap_check(const isim_handler *h, const isim_des_tap *tap, bool have_records, bool aligned) {
+  if (const int hrc = des_items_check(h)) return hrc;
   if (!have_records) return tfail("a tap needs d_records");
   if (tap->reserved[0] || tap->reserved[1]) return tfail("isim_des_tap.reserved must be 0");
   if (tap->cls > ISIM_Q_500) return tfail("the class must be ISIM_Q_ALL, ISIM_Q_200 or ISIM_Q_500");
@@ -1539,6 +1546,12 @@ int des_load_check(isim_handler *h, const isim_des_params *dp, const isim_load_p
 }
 
 }  // namespace
+
+// des_critical_path.h: the handlers isim_serve_des_spans_device refuses with a tap
+int isim::dcp::check_handler(const isim_handler *h) {
+  if (!h) return fail(ISIM_EINVAL, "DES critical path: null handler");
+  return des_items_check(h);
+}
 
 extern "C" {
 

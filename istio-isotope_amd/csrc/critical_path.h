@@ -64,6 +64,55 @@ struct HostAcc {
   void hdr(uint32_t word, uint64_t v) { add(n_services, word, v); }
 };
 
+// The script of one caller from `clock` on, over its executed children in hop order, each matched to the call
+// command whose index its position carries.  The span type supplies the children (Fold::Kids here, the DES
+// spans' in des_critical_path.h):
+//   more()             an executed child is left
+//   take(k, at, val)   call command k, sent at clock `at`: the next child if it sits at call index k (taken: its
+//                      start written or its arrival checked, `val` its H + T), else kNone with val 0
+//   win(c)             child c is a local winner
+// Returns the sum of H + T over the local winners.
+template <class Kids>
+ISIM_TW uint64_t replay_script(const ScriptView &v, uint32_t svc, uint64_t clock, Kids &kids) {
+  uint32_t k = 0;
+  uint64_t won = 0;
+  const uint32_t end = v.cmd_off[svc + 1];
+  for (uint32_t x = v.cmd_off[svc]; x < end && kids.more();) {  // (mode B: nothing follows a failed step)
+    const uint64_t c = v.cmds[x++];
+    if (cmd_is_sleep(c)) {
+      clock += c;
+    } else if (!cmd_is_conc(c)) {
+      uint64_t val;
+      const uint32_t w = kids.take(k++, clock, val);
+      if (w != kNone) {
+        kids.win(w);
+        won += val;
+      }
+      clock += val;
+    } else {
+      uint32_t n = (uint32_t)c, winner = kNone;
+      n = n < end - x ? n : end - x;
+      uint64_t longest = 0;
+      for (; n; --n) {
+        const uint64_t mc = v.cmds[x++];
+        uint64_t val = mc;
+        uint32_t w = kSleepWon;
+        if (!cmd_is_sleep(mc)) w = kids.take(k++, clock, val);
+        if (val > longest) {  // strictly: ties go to the first listed member, a zero never wins
+          longest = val;
+          winner = w;
+        }
+      }
+      if (winner < kSleepWon) {
+        kids.win(winner);
+        won += longest;
+      }
+      clock += longest;
+    }
+  }
+  return won;
+}
+
 // One trace.  begin() checks the offsets; step() handles one span of the current phase and returns
 // false once the trace is finished (folded or refused).  Every index read from a span or a link is
 // bounded before it is used, in every phase: memory safety does not depend on the spans being a walk's.
@@ -103,60 +152,33 @@ struct Fold {
     return true;
   }
 
-  // The script of caller i from `clock` on: its executed children in hop order, each matched to the call
-  // command whose index its position carries, get their start times; with `critical` the local winners
-  // get the bit.  Returns the sum of H + T over the local winners.
-  ISIM_TW uint64_t replay(uint32_t i, uint32_t svc, uint64_t clock, bool critical) {
-    uint32_t child = head(i), k = 0;
-    uint64_t won = 0;
-    const uint32_t end = v.cmd_off[svc + 1];
-    // the call command k: its executed child, if the next child sits at call index k; `val` its H + T
-    auto take = [&](uint64_t at, uint64_t &val) -> uint32_t {
-      const uint32_t kk = k++;
+  // The children of one caller as replay_script takes them: a matched child gets its start time, a
+  // local winner of a critical caller the bit
+  struct Kids {
+    Fold &f;
+    uint32_t child;
+    bool critical;
+    ISIM_TW bool more() const { return child != kNone; }
+    ISIM_TW uint32_t take(uint32_t k, uint64_t at, uint64_t &val) {
       val = 0;
       if (child == kNone) return kNone;
-      const uint32_t pos = s[child].position;
-      if (pos >= v.n_positions || kof(pos) != kk) return kNone;
+      const uint32_t pos = f.s[child].position;
+      if (pos >= f.v.n_positions || f.kof(pos) != k) return kNone;
       const uint32_t c = child;
-      child = next(c);
-      s[c].start_ns = at;
-      val = s[c].hop_ns + s[c].duration_ns;
+      child = f.next(c);
+      f.s[c].start_ns = at;
+      val = f.s[c].hop_ns + f.s[c].duration_ns;
       return c;
-    };
-    for (uint32_t x = v.cmd_off[svc]; x < end && child != kNone;) {  // (mode B: nothing follows a failed step)
-      const uint64_t c = v.cmds[x++];
-      if (cmd_is_sleep(c)) {
-        clock += c;
-      } else if (!cmd_is_conc(c)) {
-        uint64_t val;
-        const uint32_t w = take(clock, val);
-        if (w != kNone) {
-          if (critical) s[w].status |= ISIM_SPAN_CRITICAL;
-          won += val;
-        }
-        clock += val;
-      } else {
-        uint32_t n = (uint32_t)c, winner = kNone;
-        n = n < end - x ? n : end - x;
-        uint64_t longest = 0;
-        for (; n; --n) {
-          const uint64_t mc = v.cmds[x++];
-          uint64_t val = mc;
-          uint32_t w = kSleepWon;
-          if (!cmd_is_sleep(mc)) w = take(clock, val);
-          if (val > longest) {  // strictly: ties go to the first listed member, a zero never wins
-            longest = val;
-            winner = w;
-          }
-        }
-        if (winner < kSleepWon) {
-          if (critical) s[winner].status |= ISIM_SPAN_CRITICAL;
-          won += longest;
-        }
-        clock += longest;
-      }
     }
-    return won;
+    ISIM_TW void win(uint32_t c) {
+      if (critical) f.s[c].status |= ISIM_SPAN_CRITICAL;
+    }
+  };
+  // The script of caller i from `clock` on: its executed children get their start times; with `critical` the
+  // local winners get the bit.  Returns the sum of H + T over the local winners.
+  ISIM_TW uint64_t replay(uint32_t i, uint32_t svc, uint64_t clock, bool critical) {
+    Kids kids{*this, head(i), critical};
+    return replay_script(v, svc, clock, kids);
   }
 
   template <class Acc>

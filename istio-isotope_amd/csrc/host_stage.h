@@ -51,7 +51,7 @@ class HostStage {
   }
 
  private:
-  static constexpr uint32_t kMaxBufs = 5;
+  static constexpr uint32_t kMaxBufs = 6;
   bool ok(hipError_t e, const char *what) {
     if (e != hipSuccess) rc_ = set_error(ISIM_EHIP, std::string("host staging: ") + what + ": " + hipGetErrorString(e));
     return e == hipSuccess;

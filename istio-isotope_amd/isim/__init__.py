@@ -24,6 +24,7 @@ from .timeline_quantiles import (decode_timeline_quantiles, timeline_quantiles, 
 from .sketch import (decode_timeline_sketch, latency_sketch, latency_sketch_device, sketch_bins,  # noqa: F401
                      sketch_bounds, sketch_bucket, sketch_merge, sketch_quantiles, sketch_words, timeline_sketch,
                      timeline_sketch_device, timeline_sketch_out_words, timeline_sketch_table)
-from .des_spans import DES_SPAN_DTYPE, DesTrace, DesWaitTable  # noqa: F401
+from .des_spans import (DES_SPAN_DTYPE, DesCriticalPath, DesTrace, DesWaitTable,  # noqa: F401
+                        des_critical_path_device, des_critical_path_host)
 from .spans import (SPAN_DTYPE, CriticalPath, Trace, TraceSpans, select_traces, select_traces_device,  # noqa: F401
                     select_traces_host, select_workspace_bytes)

@@ -110,15 +110,21 @@ class DesHandler:
 
     def serve_spans(self, trace_begin: int, n_traces: int, q_ppm: int = 999000, min_latency_ns: int = None,
                     cls: int = native.Q_ALL, max_traces: int = 64, cap_spans: int = 2 ** 20, wide: bool = False,
-                    device: int = 0, wait_table=None):
+                    device: int = 0, wait_table=None, critical_path: bool = False):
         """Synchronous: (records, stats, DES table, [DesTrace], DesWaitTable) of one batch.  The traces: the
         records at or above the batch's q_ppm order statistic (p99.9) in class cls, or at or above
         min_latency_ns when that is given; ids ascending, the first max_traces whose spans fit cap_spans.
-        wait_table: a DesWaitTable to add into (a new one otherwise).  Item engine only."""
+        wait_table: a DesWaitTable to add into (a new one otherwise).  critical_path: a DesCriticalPath of
+        those traces is appended to the tuple, folded on the device on the batch's stream before the copy
+        back (the traces' critical spans are marked).  Item engine only."""
         from .des_spans import DES_SPAN_DTYPE, DesTrace, DesWaitTable, make_tap
         from .sim import REC_DTYPE as _REC
         names = [s["name"] for s in self.handler.graph.canonical()["services"]]
         waits = wait_table if wait_table is not None else DesWaitTable(self.handler, names=names)
+        if critical_path:
+            return self._serve_spans_critical(trace_begin, n_traces, 0 if min_latency_ns is None else min_latency_ns,
+                                              q_ppm if min_latency_ns is None else 0, cls, max_traces, cap_spans,
+                                              wide, device, waits, names)
         n_ids = min(int(max_traces), int(n_traces))
         ids, off = np.zeros(max(1, n_ids), np.uint64), np.zeros(n_ids + 1, np.uint64)
         spans = np.zeros(max(1, int(cap_spans)), DES_SPAN_DTYPE)
@@ -136,6 +142,48 @@ class DesHandler:
         traces = [DesTrace(ids[i], spans[int(off[i]):int(off[i + 1])].copy(), names) for i in range(written)]
         self.last_tap_info = info
         return recs, stats, table, traces, waits
+
+    def _serve_spans_critical(self, trace_begin, n_traces, min_latency_ns, q_ppm, cls, max_traces, cap_spans, wide,
+                              device, waits, names):
+        """serve_spans with the DES critical path: device buffers, the batch with its tap and the fold on one
+        stream, then one copy back.  32-bit rows first, and again wide if the batch asks for it."""
+        import torch
+        from . import des_spans as ds
+        from .sim import REC_DTYPE as _REC
+        n_ids = min(int(max_traces), int(n_traces))
+        cap_spans = int(cap_spans)
+        dev = torch.device("cuda", device)
+        u64 = lambda t: t.cpu().numpy().view(np.uint64)  # noqa: E731
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            z = lambda n: torch.zeros(max(1, n), dtype=torch.int64, device=dev)  # noqa: E731
+            ws = z(self.workspace_bytes(n_traces) // 8 + 1)
+            cws = z(ds.critical_path_workspace_bytes(self.handler, cap_spans) // 8)
+            for w in ([False, True] if not wide else [True]):
+                stats, table, rec = z(len(self.handler.new_stats())), z(self.table_words), z(2 * n_traces)
+                ids, off, spans, info = z(n_ids), z(n_ids + 1), z(8 * cap_spans), z(native.DES_SPAN_INFO_WORDS)
+                wt = torch.from_numpy(waits.table.view(np.int64).ravel().copy()).to(dev)
+                cpt, tw = z(ds.critical_path_table_words(self.handler)), z(n_ids)
+                tap = ds.make_tap(min_latency_ns, q_ppm, cls, n_ids, cap_spans, ids.data_ptr(), off.data_ptr(),
+                                  spans.data_ptr(), info.data_ptr(), wt.data_ptr())
+                self.serve_spans_device(trace_begin, n_traces, rec.data_ptr() if n_traces else 0, stats.data_ptr(),
+                                        table.data_ptr(), ws.data_ptr(), ws.numel() * 8, tap, stream, wide=w)
+                ds.des_critical_path_device(self.handler, off.data_ptr(), spans.data_ptr(), cap_spans, info.data_ptr(),
+                                            n_ids, cpt.data_ptr(), tw.data_ptr(), cws.data_ptr(), cws.numel() * 8, stream)
+                h_stats = u64(stats)[:len(self.handler.new_stats())]
+                if not int(h_stats[native.ST_DES_RETRY]):
+                    break
+            h_info, h_off, h_ids = u64(info), u64(off), u64(ids)
+            written = int(h_info[native.SPAN_WRITTEN])
+            h_spans = spans[:8 * int(h_off[written])].cpu().numpy().view(ds.DES_SPAN_DTYPE)
+            waits.table[...] = u64(wt).reshape(waits.table.shape)
+            path = ds.DesCriticalPath(self.handler, u64(cpt)[:ds.critical_path_table_words(self.handler)], names,
+                                      u64(tw)[:written].copy())
+            recs = rec[:2 * n_traces].cpu().numpy().view(_REC)
+            h_table = u64(table)[:max(1, self.table_words)].copy()
+        traces = [ds.DesTrace(h_ids[i], h_spans[int(h_off[i]):int(h_off[i + 1])].copy(), names) for i in range(written)]
+        self.last_tap_info = h_info
+        return recs, h_stats.copy(), h_table, traces, waits, path
 
     def arrivals(self, trace_begin: int, n_traces: int, device: int = 0) -> np.ndarray:
         """The arrival times (u64 ns since batch start) `serve` uses for these traces."""

@@ -83,6 +83,11 @@ DES_SPAN_INFO_WORDS = 5
 DW_INVOCATIONS, DW_WAITED, DW_SUM_WAIT, DW_MAX_WAIT, DW_SUM_DURATION, DW_RESP_500 = range(6)
 DW_ROW_WORDS = 6
 DW_H_TRACES, DW_H_SPANS, DW_H_SUM_LATENCY, DW_H_SUM_WAIT = range(4)
+# isim_des_critical_path*: the words of a service row and of the header row (isim.h ISIM_DCP_*)
+(DCP_INVOCATIONS, DCP_SUM_DURATION, DCP_CRITICAL, DCP_WAIT_NS, DCP_SELF_NS, DCP_HOP_NS, DCP_CRITICAL_500,
+ DCP_CRITICAL_WAITED) = range(8)
+DCP_ROW_WORDS = 8
+DCP_H_TRACES, DCP_H_SPANS, DCP_H_CRITICAL, DCP_H_SUM_LATENCY, DCP_H_REFUSED = range(5)
 
 
 def SK_BINS(s: int) -> int:
@@ -299,6 +304,13 @@ SIGNATURES = {
                                               C.c_uint64, _VP, _VP, _VP, _VP, C.c_uint64, C.POINTER(DesTap), _VP]),
     "isim_serve_des_spans": (C.c_int, [_VP, C.c_int, C.POINTER(DesParams), C.POINTER(LoadProfile), C.c_uint64,
                                        C.c_uint64, _VP, _VP, _VP, C.POINTER(DesTap)]),
+    "isim_des_critical_path_table_words": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
+    "isim_des_critical_path_workspace_bytes": (C.c_int, [_VP, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "isim_des_critical_path_merge": (C.c_int, [_VP, _VP, _VP]),
+    "isim_des_critical_path_device": (C.c_int, [_VP, _VP, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, _VP, C.c_uint64,
+                                                _VP]),
+    "isim_des_critical_path_host": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, _VP]),
+    "isim_des_critical_path": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, _VP, _VP, _VP]),
 }
 
 _lib = None
