@@ -469,6 +469,62 @@ func (h *Handler) DesCriticalPathMerge(dst, src []uint64) error {
 	return lastErr(C.isim_des_critical_path_merge(h.h, u64ptr(dst), u64ptr(src)))
 }
 
+// The service timeline (DESIGN §23): per service (windows + 2) rows of
+// SvtRowWords words (before t0, the windows, after them), then one header block.
+// Tables merge by addition except SvtMaxWait (ServiceTimelineMerge).
+const (
+	SvtArrived  = C.ISIM_SVT_ARRIVED
+	SvtStarted  = C.ISIM_SVT_STARTED
+	SvtFinished = C.ISIM_SVT_FINISHED
+	SvtSumWait  = C.ISIM_SVT_SUM_WAIT
+	SvtMaxWait  = C.ISIM_SVT_MAX_WAIT
+	SvtQueuedNs = C.ISIM_SVT_QUEUED_NS
+	SvtBusyNs   = C.ISIM_SVT_BUSY_NS
+	SvtRowWords = C.ISIM_SVT_ROW_WORDS
+	SvtHFolded  = C.ISIM_SVT_H_FOLDED
+	SvtHRefused = C.ISIM_SVT_H_REFUSED
+)
+
+func svtParams(t0Ns, windowNs uint64, nWindows uint32) C.isim_timeline_params {
+	return C.isim_timeline_params{t0_ns: C.uint64_t(t0Ns), window_ns: C.uint64_t(windowNs), n_windows: C.uint32_t(nWindows)}
+}
+
+// ServiceHolds returns per service its worker hold in ns and its replicas
+// (isim_des_service_holds): BusyNs / (window x replicas) is the utilisation.
+func (h *Handler) ServiceHolds(nServices int) ([]uint64, []uint32, error) {
+	hold, reps := make([]uint64, nServices+1), make([]uint32, nServices+1)
+	rc := C.isim_des_service_holds(h.h, u64ptr(hold), (*C.uint32_t)(unsafe.Pointer(&reps[0])))
+	if err := lastErr(rc); err != nil {
+		return nil, nil, err
+	}
+	return hold[:nServices], reps[:nServices], nil
+}
+
+// ServiceTimeline folds spans (every span of a whole tapped batch, in any
+// order) on GPU `device` into a new table (isim_service_timeline).
+func (h *Handler) ServiceTimeline(device int, spans []DesSpan, t0Ns, windowNs uint64, nWindows uint32) ([]uint64, error) {
+	p := svtParams(t0Ns, windowNs, nWindows)
+	var words C.uint64_t
+	if err := lastErr(C.isim_service_timeline_table_words(h.h, &p, &words)); err != nil {
+		return nil, err
+	}
+	table := make([]uint64, words)
+	var sp *C.isim_des_span
+	if len(spans) > 0 {
+		sp = (*C.isim_des_span)(unsafe.Pointer(&spans[0]))
+	}
+	if err := lastErr(C.isim_service_timeline(C.int(device), h.h, &p, sp, C.uint64_t(len(spans)), u64ptr(table))); err != nil {
+		return nil, err
+	}
+	return table, nil
+}
+
+// ServiceTimelineMerge adds src into dst, SvtMaxWait by max (isim_service_timeline_merge).
+func (h *Handler) ServiceTimelineMerge(dst, src []uint64, t0Ns, windowNs uint64, nWindows uint32) error {
+	p := svtParams(t0Ns, windowNs, nWindows)
+	return lastErr(C.isim_service_timeline_merge(h.h, &p, u64ptr(dst), u64ptr(src)))
+}
+
 // SelectTraces returns the ids begin + i of the records with a latency of at
 // least minLatencyNs in class cls (C.ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500), in
 // ascending i, at most maxIDs of them, and the number of matching records

@@ -1188,6 +1188,86 @@ ISIM_API int isim_des_critical_path_host(const isim_handler *h, const uint64_t *
 ISIM_API int isim_des_critical_path(int device, const isim_handler *h, const uint64_t *h_off, uint64_t n_written,
                                     isim_des_span *h_spans, uint64_t *h_table, uint64_t *h_trace_wait);
 
+/* ---- service timeline: per-service queue depth and utilisation over time (EXT) ----
+ * The timeline of isim_timeline* is the client's side of a load test.  This
+ * fold is the servers' side: the isim_des_span records of a tapped batch
+ * (threshold 0: every executed invocation) folded into a (service x window)
+ * table, the figures a Prometheus scrape of each pod gives a real run.
+ *
+ * Rows: the isim_timeline_params rules and rows of isim_timeline.  Row 0
+ * ("before") covers [0, t0); row 1 + w covers [t0 + w W, t0 + (w + 1) W) for
+ * w < n_windows; row n_windows + 1 ("after") covers everything from
+ * t0 + n_windows W on.
+ *
+ * A span v of service s with a = arrival_ns, S = start_ns, F = finish_ns has
+ * point events at a, S and F, the queue interval [a, S) and the busy interval
+ * [S, S + P_s), S + P_s saturating at 2^64 - 1; P_s is the worker hold of s,
+ * the sleep total of its script (isim_des_service_holds).
+ *
+ * The overlap of an interval with a row is the length of their intersection
+ * on the mathematical integers.  A row that would begin at or past 2^64
+ * receives nothing; t0 + n_windows W is never formed in u64; over all rows the
+ * overlaps of [x, y) sum to y - x exactly.
+ *
+ * The table: u64 [n_services][n_windows + 2][ISIM_SVT_ROW_WORDS], then one
+ * header block of ISIM_SVT_ROW_WORDS words.  ADDED into (the caller zeroes
+ * it).  Every word is a sum mod 2^64 except ISIM_SVT_MAX_WAIT, which merges by
+ * MAX: tables fold across batches, shards and GPUs, on the device by calling
+ * again and on the host with isim_service_timeline_merge.
+ *
+ * A span is refused if its service >= n_services or if a <= S <= F does not
+ * hold.  A refused span counts in ISIM_SVT_H_REFUSED and adds to nothing else;
+ * the host and the device refuse the same spans.
+ *
+ * Derived: the mean queue length of a window is QUEUED_NS / window_ns, the
+ * utilisation BUSY_NS / (window_ns x replicas), the queue depth at the end of
+ * row r the cumulative ARRIVED - STARTED over the rows <= r. */
+#define ISIM_SVT_ARRIVED   0   /* spans of s whose a falls in the row */
+#define ISIM_SVT_STARTED   1   /* spans whose S falls in it */
+#define ISIM_SVT_FINISHED  2   /* [2] spans whose F falls in it, by code (status bit 0) */
+#define ISIM_SVT_SUM_WAIT  4   /* the sum of S - a over the spans STARTED in the row */
+#define ISIM_SVT_MAX_WAIT  5   /* the largest of those (merges by MAX) */
+#define ISIM_SVT_QUEUED_NS 6   /* the sum of the overlaps of [a, S) with the row: the integral of the queue length */
+#define ISIM_SVT_BUSY_NS   7   /* the sum of the overlaps of [S, S + P_s) with the row: worker-busy time, all replicas */
+#define ISIM_SVT_ROW_WORDS 8
+/* the header block (after the last service's rows); its other words are 0 */
+#define ISIM_SVT_H_FOLDED  0   /* spans folded */
+#define ISIM_SVT_H_REFUSED 1   /* spans refused */
+#define ISIM_SVT_MAX_CELLS (1u << 24)   /* n_services * (n_windows + 2) at most */
+
+/* Every call below returns ISIM_EINVAL, before any HIP call, for a handler
+ * isim_serve_des_spans_device refuses with a tap, a null argument, parameters
+ * isim_timeline refuses, or n_services * (n_windows + 2) above ISIM_SVT_MAX_CELLS. */
+/* host only, no GPU: per service its worker hold P_s in ns and its replicas (at least 1); [n_services] each */
+ISIM_API int isim_des_service_holds(const isim_handler *h, uint64_t *hold_ns, uint32_t *replicas);
+/* host only, no GPU: (n_services * (n_windows + 2) + 1) * ISIM_SVT_ROW_WORDS */
+ISIM_API int isim_service_timeline_table_words(const isim_handler *h, const isim_timeline_params *p, uint64_t *words);
+/* host only, no GPU: 16 bytes per (service, row), at least 64 */
+ISIM_API int isim_service_timeline_workspace_bytes(const isim_handler *h, const isim_timeline_params *p,
+                                                   uint64_t *bytes);
+/* host only, no GPU: dst[w] += src[w], ISIM_SVT_MAX_WAIT of the rows by MAX */
+ISIM_API int isim_service_timeline_merge(const isim_handler *h, const isim_timeline_params *p, uint64_t *dst,
+                                         const uint64_t *src);
+/* The fold of the spans that a preceding isim_serve_des_spans_device wrote to
+ * d_spans, on the current device, asynchronously on hip_stream.  The span
+ * count is read on the device: d_off[d_info[ISIM_SPAN_WRITTEN]], bounded by
+ * cap_spans (which sizes the grid); d_off and d_info are the tap's.  ADDS into
+ * d_table.  No host synchronisation, graph-capturable from the first call,
+ * the workspace may be dirty (calls that share one must be ordered).
+ * cap_spans 0 does nothing.  Also ISIM_EINVAL: cap_spans above 2^40, buffers
+ * not 8-byte aligned (d_spans 16), a workspace below
+ * isim_service_timeline_workspace_bytes. */
+ISIM_API int isim_service_timeline_device(const isim_handler *h, const isim_timeline_params *p, const uint64_t *d_off,
+                                          const isim_des_span *d_spans, uint64_t cap_spans, const uint64_t *d_info,
+                                          uint64_t *d_table, void *d_workspace, uint64_t workspace_bytes,
+                                          void *hip_stream);
+/* host only, no GPU: the same fold on the CPU over h_spans[0 .. n_spans); ADDS into h_table */
+ISIM_API int isim_service_timeline_host(const isim_handler *h, const isim_timeline_params *p,
+                                        const isim_des_span *h_spans, uint64_t n_spans, uint64_t *h_table);
+/* Synchronous convenience: host buffers, on GPU `device`. */
+ISIM_API int isim_service_timeline(int device, const isim_handler *h, const isim_timeline_params *p,
+                                   const isim_des_span *h_spans, uint64_t n_spans, uint64_t *h_table);
+
 #ifdef __cplusplus
 }
 #endif

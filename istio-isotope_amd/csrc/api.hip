@@ -24,6 +24,7 @@
 #include "kernel_abi.h"
 #include "load_profile.h"
 #include "program.h"
+#include "service_timeline.h"
 #include "spans.h"
 
 namespace {
@@ -1550,6 +1551,12 @@ int des_load_check(isim_handler *h, const isim_des_params *dp, const isim_load_p
 // des_critical_path.h: the handlers isim_serve_des_spans_device refuses with a tap
 int isim::dcp::check_handler(const isim_handler *h) {
   if (!h) return fail(ISIM_EINVAL, "DES critical path: null handler");
+  return des_items_check(h);
+}
+
+// service_timeline.h: the same handlers
+int isim::svt::check_handler(const isim_handler *h) {
+  if (!h) return fail(ISIM_EINVAL, "service timeline: null handler");
   return des_items_check(h);
 }
 

@@ -240,6 +240,9 @@ void des_row_traffic(const DesPlan &plan, uint32_t &reads, uint32_t &writes);
 // Returns ISIM_OK or ISIM_EINVAL with the reason in `err` when the graph is
 // outside the DES class.
 int build_des_plan(const ServiceGraph &g, const Program &p, bool modeb, DesPlan &out, std::string &err);
+// Per service of the graph its worker hold time, DesPos::hold of its positions: the sum of every sleep of
+// its script (the service timeline's busy interval).
+std::vector<uint64_t> des_service_holds(const ServiceGraph &g);
 
 // The item engine (des_items.hip): one batch of a dynamic walk's DES.  Device
 // per-trace workspace bytes; the per-item arrays are allocated on `stream`

@@ -72,6 +72,12 @@ ScriptShape shape_of(const Service &s) {
 
 }  // namespace
 
+std::vector<uint64_t> des_service_holds(const ServiceGraph &g) {
+  std::vector<uint64_t> hold;
+  for (const Service &s : g.services) hold.push_back(shape_of(s).hold);
+  return hold;
+}
+
 void des_row_traffic(const DesPlan &plan, uint32_t &reads, uint32_t &writes) {
   reads = writes = 0;
   const uint32_t np = (uint32_t)plan.pos.size();

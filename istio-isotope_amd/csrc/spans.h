@@ -165,7 +165,7 @@ struct SpanSink : NoStats {
 const char *handler_error(const Program &p);
 
 // ---- device side (spans.hip).  The handler's tables on a device: the tree's nodes, per-position facts, the
-// slot-to-callee table and the flat scripts (critical_path.h); uploaded once per (handler, device) at the first
+// slot-to-callee table, the flat scripts (critical_path.h) and the services' worker holds (des.h); uploaded once per (handler, device) at the first
 // call that needs them, under a relaxed capture mode, so that call may itself be a captured one
 struct DevTables {
   void *nodes = nullptr;
@@ -174,6 +174,7 @@ struct DevTables {
   uint32_t *slot_callee = nullptr;
   uint32_t *cmd_off = nullptr;
   uint64_t *cmds = nullptr;
+  uint64_t *svc_hold = nullptr;  // [n_services]: des_service_holds
 };
 int device_tables(const HandlerView &v, DevTables &out);  // of the current device; ISIM_OK or ISIM_EHIP
 

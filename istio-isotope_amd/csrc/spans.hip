@@ -28,6 +28,7 @@
 #include "hip_check.h"
 #include "host_stage.h"
 #include "critical_path.h"
+#include "des.h"
 #include "spans.h"
 #include "trace_rec_dev.h"
 
@@ -298,7 +299,8 @@ WalkFn walk_kernel(Frames fr, bool t64, bool modeb, bool wide, bool emit) {
 // ---- the handler's tables on a device (spans.h DevTables), kept in the handler (HandlerView::state) and freed
 // with it
 void free_tables(const DevTables &t) {
-  for (void *q : {t.nodes, (void *)t.ext, (void *)t.step, (void *)t.slot_callee, (void *)t.cmd_off, (void *)t.cmds})
+  for (void *q : {t.nodes, (void *)t.ext, (void *)t.step, (void *)t.slot_callee, (void *)t.cmd_off, (void *)t.cmds,
+                  (void *)t.svc_hold})
     if (q) (void)hipFree(q);
 }
 struct State {
@@ -342,6 +344,7 @@ int device_tables(const HandlerView &v, DevTables &out) {
   const Program &p = *v.prog;
   const std::vector<uint32_t> callee(p.slot_callee.begin(), p.slot_callee.end());
   const cp::FlatScripts scripts = cp::flat_scripts(*v.graph);
+  const std::vector<uint64_t> hold = des_service_holds(*v.graph);
   RelaxedCapture relaxed;
   hipStream_t s = nullptr;
   ISIM_HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -353,6 +356,7 @@ int device_tables(const HandlerView &v, DevTables &out) {
   if (rc == ISIM_OK) rc = upload((void **)&t.slot_callee, callee.data(), callee.size() * sizeof(uint32_t), s);
   if (rc == ISIM_OK) rc = upload((void **)&t.cmd_off, scripts.cmd_off.data(), scripts.cmd_off.size() * sizeof(uint32_t), s);
   if (rc == ISIM_OK) rc = upload((void **)&t.cmds, scripts.cmds.data(), scripts.cmds.size() * sizeof(uint64_t), s);
+  if (rc == ISIM_OK) rc = upload((void **)&t.svc_hold, hold.data(), hold.size() * sizeof(uint64_t), s);
   if (rc == ISIM_OK && hipStreamSynchronize(s) != hipSuccess) rc = set_error(ISIM_EHIP, "trace spans: table upload failed");
   (void)hipStreamDestroy(s);
   if (rc != ISIM_OK) {

@@ -61,36 +61,10 @@ struct TlArgs {
 // the table row of time x (timeline_row.h)
 __device__ __forceinline__ uint32_t tl_row(const TlArgs &a, uint64_t x) { return isim::tl::row_of(a, x); }
 
-// ---- wave reductions (all 64 lanes active): row shifts, then the row totals
-// broadcast into the later rows; lane 63 holds the result.  0 is the identity
-// of both operations, so lanes without a source read 0.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint64_t dpp_u64(uint64_t v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROW_MASK, 0xF, false);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROW_MASK, 0xF, false);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t lane63(uint64_t v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
-  return ((uint64_t)hi << 32) | lo;
-}
-struct OpAdd {
-  __device__ static uint64_t f(uint64_t a, uint64_t b) { return a + b; }
-};
-struct OpMax {
-  __device__ static uint64_t f(uint64_t a, uint64_t b) { return a > b ? a : b; }
-};
-template <typename Op>
-__device__ __forceinline__ uint64_t wave_reduce(uint64_t v) {
-  v = Op::f(v, dpp_u64<0x111, 0xF>(v));  // row_shr:1
-  v = Op::f(v, dpp_u64<0x112, 0xF>(v));  // row_shr:2
-  v = Op::f(v, dpp_u64<0x114, 0xF>(v));  // row_shr:4
-  v = Op::f(v, dpp_u64<0x118, 0xF>(v));  // row_shr:8
-  v = Op::f(v, dpp_u64<0x142, 0xA>(v));  // row_bcast:15 into rows 1, 3
-  v = Op::f(v, dpp_u64<0x143, 0xC>(v));  // row_bcast:31 into rows 2, 3
-  return lane63(v);
-}
+// the wave reductions of wave_peel.h
+using isim::dev::OpAdd;
+using isim::dev::OpMax;
+using isim::dev::wave_reduce;
 
 // ---- one update of word `off` of table row `row`: the LDS run or the table
 struct Tile {

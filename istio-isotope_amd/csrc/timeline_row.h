@@ -1,11 +1,19 @@
 // The row arithmetic of the timeline tables (include/isim.h isim_timeline_params,
 // DESIGN.md §14), shared by timeline.hip and timeline_quantiles.hip: the
 // parameter rules, the exact u64 division by the window and the row of a time.
+// service_timeline.h reads it on the host as well.
 #pragma once
 
 #include <cstdint>
 
 #include "../../include/isim.h"
+#include "host_device.h"
+
+#if defined(__HIPCC__)
+#define ISIM_TL_FN __host__ __device__ __forceinline__
+#else
+#define ISIM_TL_FN inline
+#endif
 
 namespace isim {
 namespace tl {
@@ -57,7 +65,7 @@ inline void set_row_args(A &a, const isim_timeline_params &p) {
 
 // the table row of time x: 0 before t0, 1 + w for window w, n_windows + 1 after the last
 template <typename A>
-__device__ __forceinline__ uint32_t row_of(const A &a, uint64_t x) {
+ISIM_TL_FN uint32_t row_of(const A &a, uint64_t x) {
   if (x < a.t0) return 0u;
   const uint64_t d = x - a.t0;
   const uint64_t w = a.pow2 ? d >> a.shift : div_recip(d, a.window, a.recip);

@@ -1,6 +1,7 @@
 // The ballot peel: lanes of a wave that update the same
 // word act once.  Shared by quantile.hip and timeline_quantiles.hip (through
-// radix_select.h's wave_add), and by timeline.hip.
+// radix_select.h's wave_add), and by timeline.hip and service_timeline.hip,
+// which also share the DPP reductions below for their SUM and MAX words.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,6 +38,37 @@ __device__ __forceinline__ void wave_peel(uint32_t key, uint32_t none, Shared sh
     rem &= ~m;
   }
   if (key != none) alone(key);
+}
+
+// ---- wave reductions (all 64 lanes active): row shifts, then the row totals
+// broadcast into the later rows; lane 63 holds the result, which every lane
+// gets.  0 is the identity of both operations, so lanes without a source read 0.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint64_t dpp_u64(uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROW_MASK, 0xF, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROW_MASK, 0xF, false);
+  return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t lane63(uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
+  return ((uint64_t)hi << 32) | lo;
+}
+struct OpAdd {
+  __device__ static uint64_t f(uint64_t a, uint64_t b) { return a + b; }
+};
+struct OpMax {
+  __device__ static uint64_t f(uint64_t a, uint64_t b) { return a > b ? a : b; }
+};
+template <typename Op>
+__device__ __forceinline__ uint64_t wave_reduce(uint64_t v) {
+  v = Op::f(v, dpp_u64<0x111, 0xF>(v));  // row_shr:1
+  v = Op::f(v, dpp_u64<0x112, 0xF>(v));  // row_shr:2
+  v = Op::f(v, dpp_u64<0x114, 0xF>(v));  // row_shr:4
+  v = Op::f(v, dpp_u64<0x118, 0xF>(v));  // row_shr:8
+  v = Op::f(v, dpp_u64<0x142, 0xA>(v));  // row_bcast:15 into rows 1, 3
+  v = Op::f(v, dpp_u64<0x143, 0xC>(v));  // row_bcast:31 into rows 2, 3
+  return lane63(v);
 }
 
 }  // namespace dev

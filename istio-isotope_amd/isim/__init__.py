@@ -28,3 +28,6 @@ from .des_spans import (DES_SPAN_DTYPE, DesCriticalPath, DesTrace, DesWaitTable,
                         des_critical_path_device, des_critical_path_host)
 from .spans import (SPAN_DTYPE, CriticalPath, Trace, TraceSpans, select_traces, select_traces_device,  # noqa: F401
                     select_traces_host, select_workspace_bytes)
+from .service_timeline import (ServiceTimeline, service_holds, service_timeline, service_timeline_device,  # noqa: F401
+                               service_timeline_host, service_timeline_table_words,
+                               service_timeline_workspace_bytes)

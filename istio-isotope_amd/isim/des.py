@@ -185,6 +185,53 @@ class DesHandler:
         self.last_tap_info = h_info
         return recs, h_stats.copy(), h_table, traces, waits, path
 
+    def service_timeline(self, trace_begin: int, n_traces: int, window_ns: int, n_windows: int, t0_ns: int = 0,
+                         device: int = 0, into=None, cap_spans: int = None):
+        """The ServiceTimeline of one batch: the whole batch tapped (threshold 0, every trace,
+        room for hops_upper spans per trace unless cap_spans says otherwise) and folded on the same stream;
+        only the table comes back.  into: a ServiceTimeline of the same parameters to add into (a new one
+        otherwise).  32-bit rows first, and again wide if the batch asks for it.  Raises if the spans did
+        not fit cap_spans: never a partial table.  Item engine only."""
+        import torch
+        from . import des_spans as ds
+        from .service_timeline import (ServiceTimeline, service_timeline_device,
+                                       service_timeline_workspace_bytes)
+        if into is None:
+            into = ServiceTimeline(self.handler, window_ns, n_windows, t0_ns)
+        elif (into.window_ns, into.n_windows, into.t0_ns) != (int(window_ns), int(n_windows), int(t0_ns)):
+            raise ValueError("`into` has other timeline parameters")
+        n_traces = int(n_traces)
+        cap = n_traces * int(self.handler.info.hops_upper) if cap_spans is None else int(cap_spans)
+        dev = torch.device("cuda", device)
+        u64 = lambda t: t.cpu().numpy().view(np.uint64)  # noqa: E731
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            z = lambda n: torch.zeros(max(1, n), dtype=torch.int64, device=dev)  # noqa: E731
+            ws = z(self.workspace_bytes(n_traces) // 8 + 1)
+            tws = z(service_timeline_workspace_bytes(self.handler, window_ns, n_windows, t0_ns) // 8)
+            for w in [False, True]:
+                stats, table, rec = z(len(self.handler.new_stats())), z(self.table_words), z(2 * n_traces)
+                ids, off, spans, info = z(n_traces), z(n_traces + 1), z(8 * cap), z(native.DES_SPAN_INFO_WORDS)
+                out = torch.from_numpy(into.flat.view(np.int64).copy()).to(dev)
+                tap = ds.make_tap(0, 0, native.Q_ALL, n_traces, cap, ids.data_ptr(), off.data_ptr(), spans.data_ptr(),
+                                  info.data_ptr())
+                self.serve_spans_device(trace_begin, n_traces, rec.data_ptr() if n_traces else 0, stats.data_ptr(),
+                                        table.data_ptr(), ws.data_ptr(), ws.numel() * 8, tap, stream, wide=w)
+                service_timeline_device(self.handler, window_ns, n_windows, t0_ns, off.data_ptr(),
+                                            spans.data_ptr(), cap, info.data_ptr(), out.data_ptr(), tws.data_ptr(),
+                                            tws.numel() * 8, stream)
+                if not int(u64(stats)[native.ST_DES_RETRY]):
+                    break
+            h_info = u64(info)
+            h_out = u64(out)
+        self.last_tap_info = h_info
+        if int(h_info[native.DES_SPAN_MATCHES]) != int(h_info[native.SPAN_WRITTEN]):
+            raise RuntimeError(f"service_timeline: the batch has {int(h_info[native.SPAN_TOTAL])} spans, cap_spans "
+                               f"{cap} holds {int(h_info[native.SPAN_WRITTEN])} of its "
+                               f"{int(h_info[native.DES_SPAN_MATCHES])} traces")
+        into.flat[...] = h_out[:into.flat.size]
+        return into
+
     def arrivals(self, trace_begin: int, n_traces: int, device: int = 0) -> np.ndarray:
         """The arrival times (u64 ns since batch start) `serve` uses for these traces."""
         if self.profile is not None:

@@ -88,6 +88,11 @@ DW_H_TRACES, DW_H_SPANS, DW_H_SUM_LATENCY, DW_H_SUM_WAIT = range(4)
  DCP_CRITICAL_WAITED) = range(8)
 DCP_ROW_WORDS = 8
 DCP_H_TRACES, DCP_H_SPANS, DCP_H_CRITICAL, DCP_H_SUM_LATENCY, DCP_H_REFUSED = range(5)
+# isim_service_timeline*: the words of a (service, row) cell and of the header block (isim.h ISIM_SVT_*)
+SVT_ARRIVED, SVT_STARTED, SVT_FINISHED, SVT_SUM_WAIT, SVT_MAX_WAIT, SVT_QUEUED_NS, SVT_BUSY_NS = 0, 1, 2, 4, 5, 6, 7
+SVT_ROW_WORDS = 8
+SVT_H_FOLDED, SVT_H_REFUSED = 0, 1
+SVT_MAX_CELLS = 1 << 24
 
 
 def SK_BINS(s: int) -> int:
@@ -311,6 +316,14 @@ SIGNATURES = {
                                                 _VP]),
     "isim_des_critical_path_host": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, _VP]),
     "isim_des_critical_path": (C.c_int, [C.c_int, _VP, _VP, C.c_uint64, _VP, _VP, _VP]),
+    "isim_des_service_holds": (C.c_int, [_VP, _VP, _VP]),
+    "isim_service_timeline_table_words": (C.c_int, [_VP, C.POINTER(TimelineParams), C.POINTER(C.c_uint64)]),
+    "isim_service_timeline_workspace_bytes": (C.c_int, [_VP, C.POINTER(TimelineParams), C.POINTER(C.c_uint64)]),
+    "isim_service_timeline_merge": (C.c_int, [_VP, C.POINTER(TimelineParams), _VP, _VP]),
+    "isim_service_timeline_device": (C.c_int, [_VP, C.POINTER(TimelineParams), _VP, _VP, C.c_uint64, _VP, _VP, _VP,
+                                               C.c_uint64, _VP]),
+    "isim_service_timeline_host": (C.c_int, [_VP, C.POINTER(TimelineParams), _VP, C.c_uint64, _VP]),
+    "isim_service_timeline": (C.c_int, [C.c_int, _VP, C.POINTER(TimelineParams), _VP, C.c_uint64, _VP]),
 }
 
 _lib = None
