@@ -268,7 +268,8 @@ constexpr uint32_t kStageMaxSlots = 1u << 16;
 // slot (zero tail padding, as the stream's).  Streams whose kWorkSlots tables
 // exceed kGroupTableMaxBytes get none and keep the in-kernel scalar rounds.
 struct GroupEnt {
-  uint32_t uk0, uk1, d;  // philox_lockstep's round-2 words of the group
+  uint32_t uk0, uk1;     // philox_lockstep's round-2 words of the group (keys folded in)
+  uint32_t d;            // lo(M0 u0) ^ (seed_hi + 2 W1): the round-2 word d with round 3's key folded in
   uint32_t flags;        // kGroupAnyThr | kGroupAnyAlways
 };
 static_assert(sizeof(GroupEnt) == 16, "GroupEnt must be 16 bytes");

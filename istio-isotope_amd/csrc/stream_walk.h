@@ -80,19 +80,69 @@ __device__ __forceinline__ void site_err_add(const Ctx &c, uint32_t slot, uint32
   else atomicAdd((unsigned long long *)(c.gstats + ISIM_ST_SITES + c.n_slots + slot), (unsigned long long)v);
 }
 
+// Round keys of the lockstep draws (philox_lockstep_from).  Rounds 1-2 run on
+// the wave-uniform words and round 3's keys are folded into its operands, so
+// the vector rounds that take a key are rounds 4-10.  The keys of the first
+// NH of them are held in VGPRs for the whole batch (wave-uniform values; a
+// VOP3 takes three VGPR sources, so they cost no instruction); the later
+// rounds add theirs up in scalar code in every group (2 s_add each).  They do
+// not go into SGPRs: the kernels sit at their SGPR cap, and held scalar keys
+// spill to VGPR lanes and come back as v_readlane (VALU).
+// NH per walker: what its kernels' VGPR budget (64 at ISIM_STREAM_WAVES 8)
+// holds with no scratch and no v_readlane added to a group loop.
+#ifndef ISIM_HELD_A
+#define ISIM_HELD_A 4
+#endif
+#ifndef ISIM_HELD_MARK
+#define ISIM_HELD_MARK 7
+#endif
+#ifndef ISIM_HELD_CL
+#define ISIM_HELD_CL 2
+#endif
+#ifndef ISIM_HELD_STACK
+#define ISIM_HELD_STACK 3
+#endif
+constexpr int kHeldA = ISIM_HELD_A;          // walk_stream_a (kind 4, mode A)
+constexpr int kHeldMark = ISIM_HELD_MARK;    // walk_stream_mark (kind 8)
+constexpr int kHeldCl = ISIM_HELD_CL;        // walk_stream_cl (kind 6)
+constexpr int kHeldStack = ISIM_HELD_STACK;  // walk_stream (kinds 4 and 5, mode B)
+constexpr int kFirstKeyRound = 3;  // 0-based: rounds 0-1 scalar, round 2 keyless
+template <int NH>
+struct HeldKeys {
+  static_assert(NH >= 0 && NH <= 10 - kFirstKeyRound, "rounds 4-10 take a key");
+  uint32_t k0[NH > 0 ? NH : 1], k1[NH > 0 ? NH : 1];
+  __device__ __forceinline__ HeldKeys(uint32_t k0a, uint32_t k1a) {
+#pragma unroll
+    for (int i = 0; i < NH; ++i) {
+      k0[i] = k0a + (uint32_t)(kFirstKeyRound + i) * W0;
+      k1[i] = k1a + (uint32_t)(kFirstKeyRound + i) * W1;
+      // opaque VGPR values: neither rematerialised as s_add in the group
+      // loop nor read back into SGPRs
+      asm volatile("" : "+v"(k0[i]), "+v"(k1[i]));
+    }
+  }
+};
+
 // TPL traces per lane: the wave walks 64*TPL traces through one pass over the
 // stream, so the per-record scalar work (fetch, decode, counter adds) is
 // shared and each lane runs TPL independent Philox chains (ILP).  Trace u of
 // a lane is trace base + 64 u + lane of the launch.
-template <int TPL>
+template <int TPL, int NH>
 struct StreamBatch {
   uint64_t idx[TPL], all[TPL];  // index in the launch; ballot of valid
   uint32_t t_lo[TPL], t_hi[TPL];
   uint32_t t_hi_u;  // t_hi of the batch when hi_uniform
   bool valid[TPL];
   bool hi_uniform = true;
+  HeldKeys<NH> keys;  // the lockstep draws' held round keys
+  // the lockstep draws' round-2 word c1 of each trace (it depends on t_lo
+  // alone) with round 3's key folded in.  Formed here, opaque: written next to
+  // its use, the compiler re-associates the xor chain and pays a second xor
+  // per trace in every group
+  uint32_t bk[TPL];
 
-  __device__ __forceinline__ StreamBatch(uint64_t trace_begin, uint64_t n_traces, uint64_t base) {
+  __device__ __forceinline__ StreamBatch(const Ctx &c, uint64_t trace_begin, uint64_t n_traces, uint64_t base)
+      : keys(c.k0, c.k1) {
     const uint32_t lane = lane_id();
     uint32_t hi_u[TPL];
 #pragma unroll
@@ -108,6 +158,9 @@ struct StreamBatch {
       // fold into scalar math
       hi_uniform = hi_uniform && ballot(t_hi[u] != hi_u[u]) == 0 && hi_u[u] == hi_u[0];
       all[u] = ballot(valid[u]);
+      const uint32_t v2 = (uint32_t)(((uint64_t)M0 * t_lo[u]) >> 32) ^ c.k1;
+      bk[u] = (uint32_t)((uint64_t)M1 * v2) ^ (c.k0 + 2u * W0);
+      asm volatile("" : "+v"(bk[u]));
     }
     t_hi_u = hi_u[0];
   }
@@ -119,7 +172,8 @@ struct StreamBatch {
 };
 
 // Rounds 1-2 of the wave-uniform counter words (t_hi, g, 0) of a group's
-// Philox blocks: what the vector rounds need of them, as GroupEnt's words.
+// Philox blocks: what the vector rounds need of them, as GroupEnt's words
+// (d with round 3's key folded in: the word is used nowhere else).
 // Shared by the walkers (scalar code, per wave and group) and the launch's
 // group table (isim_group_table, once per group).
 __host__ __device__ __forceinline__ void philox_uniform_rounds(uint32_t t_hi_u, uint32_t g, uint32_t k0a, uint32_t k1a,
@@ -131,37 +185,52 @@ __host__ __device__ __forceinline__ void philox_uniform_rounds(uint32_t t_hi_u, 
   const uint64_t q0 = (uint64_t)M0 * u0;                     // scalar (round 2)
   uk0 = u1 ^ k0b;
   uk1 = (uint32_t)(q0 >> 32) ^ k1b;
-  d = (uint32_t)q0;
+  d = (uint32_t)q0 ^ (k1a + 2u * W1);
 }
 
 // TPL Philox blocks (one per trace of the lane) of counter (t_lo[u], t_hi, g, 0)
-// in lockstep, given rounds 1-2 of the wave-uniform words (uk0, uk1, d): the
+// in lockstep, given rounds 1-2 of the wave-uniform words (uk0, uk1, dk): the
 // round keys are shared by the TPL chains.
-template <int TPL>
-__device__ __forceinline__ void philox_lockstep_from(const uint32_t (&t_lo)[TPL], uint32_t k0a, uint32_t k1a,
-                                                     uint32_t uk0, uint32_t uk1, uint32_t d0, uint32_t (&x)[TPL][4]) {
+template <int TPL, int NH>
+__device__ __forceinline__ void philox_lockstep_from(const StreamBatch<TPL, NH> &bt, uint32_t k0a, uint32_t k1a,
+                                                     uint32_t uk0, uint32_t uk1, uint32_t dk, uint32_t (&x)[TPL][4]) {
   uint32_t a[TPL], b[TPL], cc[TPL], d[TPL];
+  // round 3 without keys: k1 + 2 W1 is in dk and k0 + 2 W0 in the batch's bk.
+  // Two-input xors, and no v_mov to bring the wave-uniform d next to a
+  // scalar key.
 #pragma unroll
   for (int u = 0; u < TPL; ++u) {
-    const uint64_t p0 = (uint64_t)M0 * t_lo[u];              // per lane
+    const uint64_t p0 = (uint64_t)M0 * bt.t_lo[u];           // per lane
     const uint32_t v2 = (uint32_t)(p0 >> 32) ^ k1a;
     const uint64_t p1 = (uint64_t)M1 * v2;
-    a[u] = (uint32_t)(p1 >> 32) ^ uk0;
-    b[u] = (uint32_t)p1;
-    cc[u] = (uint32_t)p0 ^ uk1;
-    d[u] = d0;
+    const uint32_t bk = bt.bk[u];
+    const uint32_t a2 = (uint32_t)(p1 >> 32) ^ uk0;
+    const uint32_t c2 = (uint32_t)p0 ^ uk1;
+    const uint64_t r0 = (uint64_t)M0 * a2;
+    const uint64_t r1 = (uint64_t)M1 * c2;
+    a[u] = (uint32_t)(r1 >> 32) ^ bk;
+    b[u] = (uint32_t)r1;
+    cc[u] = (uint32_t)(r0 >> 32) ^ dk;
+    d[u] = (uint32_t)r0;
   }
-  uint32_t k0 = k0a + 2u * W0, k1 = k1a + 2u * W1;
 #pragma unroll
-  for (int r = 2; r < 10; ++r) {
-    // recompute the round keys per group (2 s_add) instead of letting the
-    // compiler hoist all 16 into SGPRs, which spill to VGPR lanes and come
-    // back as v_readlane (VALU) in the hot loop
-    asm volatile("" : "+s"(k0), "+s"(k1));
+  for (int i = 0; i < NH; ++i) {
 #pragma unroll
-    for (int u = 0; u < TPL; ++u) round1(a[u], b[u], cc[u], d[u], k0, k1);
-    k0 += W0;
-    k1 += W1;
+    for (int u = 0; u < TPL; ++u) round1(a[u], b[u], cc[u], d[u], bt.keys.k0[i], bt.keys.k1[i]);
+  }
+  if constexpr (kFirstKeyRound + NH < 10) {
+    uint32_t k0 = k0a + (uint32_t)(kFirstKeyRound + NH) * W0;
+    uint32_t k1 = k1a + (uint32_t)(kFirstKeyRound + NH) * W1;
+#pragma unroll
+    for (int r = kFirstKeyRound + NH; r < 10; ++r) {
+      // recompute these round keys per group (2 s_add) instead of letting the
+      // compiler hoist them into SGPRs (HeldKeys)
+      asm volatile("" : "+s"(k0), "+s"(k1));
+#pragma unroll
+      for (int u = 0; u < TPL; ++u) round1(a[u], b[u], cc[u], d[u], k0, k1);
+      k0 += W0;
+      k1 += W1;
+    }
   }
 #pragma unroll
   for (int u = 0; u < TPL; ++u) {
@@ -174,15 +243,15 @@ __device__ __forceinline__ void philox_lockstep_from(const uint32_t (&t_lo)[TPL]
 
 // ... with the scalar rounds 1-2 computed here (all counter words but t_lo
 // are wave-uniform): the batches without a group table.
-template <int TPL>
-__device__ __forceinline__ void philox_lockstep(const uint32_t (&t_lo)[TPL], uint32_t t_hi_u, uint32_t g,
-                                                uint32_t k0a, uint32_t k1a, uint32_t (&x)[TPL][4]) {
-  uint32_t uk0, uk1, d;
-  philox_uniform_rounds(t_hi_u, g, k0a, k1a, uk0, uk1, d);
+template <int TPL, int NH>
+__device__ __forceinline__ void philox_lockstep(const StreamBatch<TPL, NH> &bt, uint32_t g, uint32_t k0a, uint32_t k1a,
+                                                uint32_t (&x)[TPL][4]) {
+  uint32_t uk0, uk1, dk;
+  philox_uniform_rounds(bt.t_hi_u, g, k0a, k1a, uk0, uk1, dk);
   // a VOP3 reads one SGPR: pre-xor the uniform words (opaque, so the
   // compiler does not re-fold them into a two-SGPR v_bitop3 + v_mov)
-  asm volatile("" : "+s"(uk0), "+s"(uk1));
-  philox_lockstep_from<TPL>(t_lo, k0a, k1a, uk0, uk1, d, x);
+  asm volatile("" : "+s"(uk0), "+s"(uk1), "+s"(dk));
+  philox_lockstep_from<TPL, NH>(bt, k0a, k1a, uk0, uk1, dk, x);
 }
 
 __device__ __forceinline__ uint32_t thr_or(const Node4 &q) {
@@ -194,14 +263,14 @@ __device__ __forceinline__ uint32_t thr_or(const Node4 &q) {
 // when no record of the group has a threshold (thr_any == 0: nothing compares
 // below 0).  hi_uniform is the batch's flag: a walker that instantiates its
 // loop per value passes a constant and the test folds away.
-template <int TPL>
-__device__ __forceinline__ void stream_draws(const Ctx &c, const StreamBatch<TPL> &bt, bool hi_uniform,
+template <int TPL, int NH>
+__device__ __forceinline__ void stream_draws(const Ctx &c, const StreamBatch<TPL, NH> &bt, bool hi_uniform,
                                              uint32_t thr_any, uint32_t g, uint32_t (&x)[TPL][4]) {
 #pragma unroll
   for (int u = 0; u < TPL; ++u) x[u][0] = x[u][1] = x[u][2] = x[u][3] = 0;
   if (thr_any != 0) {
     if (hi_uniform) {
-      philox_lockstep<TPL>(bt.t_lo, bt.t_hi_u, g, c.k0, c.k1, x);
+      philox_lockstep<TPL, NH>(bt, g, c.k0, c.k1, x);
     } else {
 #pragma unroll
       for (int u = 0; u < TPL; ++u) {
@@ -217,11 +286,11 @@ __device__ __forceinline__ void stream_draws(const Ctx &c, const StreamBatch<TPL
 // The same draws from the group's table entry (the batch is hi_uniform and
 // its t_hi is the table's): no scalar rounds, and the threshold test is a bit
 // of the entry.
-template <int TPL>
-__device__ __forceinline__ void stream_draws_tab(const Ctx &c, const StreamBatch<TPL> &bt, const GroupEnt &e,
+template <int TPL, int NH>
+__device__ __forceinline__ void stream_draws_tab(const Ctx &c, const StreamBatch<TPL, NH> &bt, const GroupEnt &e,
                                                  uint32_t (&x)[TPL][4]) {
   if (e.flags & kGroupAnyThr) {
-    philox_lockstep_from<TPL>(bt.t_lo, c.k0, c.k1, e.uk0, e.uk1, e.d, x);
+    philox_lockstep_from<TPL, NH>(bt, c.k0, c.k1, e.uk0, e.uk1, e.d, x);
   } else {
     // the zeros stay in this (rare) branch: written before the test, as
     // `x = 0; if (...) philox`, they were 4 TPL v_mov in every group
@@ -235,8 +304,8 @@ __device__ __forceinline__ void stream_draws_tab(const Ctx &c, const StreamBatch
 // A batch draws from the launch's group table when there is one, the batch
 // does not straddle 2^32 and its t_hi is the one the table was built for (a
 // launch that crosses 2^32: the batches before the crossing).
-template <int TPL>
-__device__ __forceinline__ bool use_group_table(const StreamBatch<TPL> &bt, CEnt *tab, uint32_t tab_t_hi) {
+template <int TPL, int NH>
+__device__ __forceinline__ bool use_group_table(const StreamBatch<TPL, NH> &bt, CEnt *tab, uint32_t tab_t_hi) {
   return tab != nullptr && bt.hi_uniform && bt.t_hi_u == tab_t_hi;
 }
 
@@ -317,7 +386,7 @@ __device__ __forceinline__ void walk_stream(const Ctx &c, CNode4 *__restrict__ s
                                             uint32_t n_nodes, uint64_t t_static, uint64_t trace_begin,
                                             uint64_t n_traces, uint64_t base, CEnt *__restrict__ tab,
                                             uint32_t tab_t_hi) {
-  const StreamBatch<TPL> bt(trace_begin, n_traces, base);
+  const StreamBatch<TPL, kHeldStack> bt(c, trace_begin, n_traces, base);
   const bool lane0 = lane_id() == 0;
   uint32_t errh[TPL];
   uint64_t root_st[TPL];
@@ -509,7 +578,7 @@ __device__ __forceinline__ void walk_stream_a(const Ctx &c, CNode4 *__restrict__
                                               uint64_t n_traces, uint64_t base,
                                               const uint32_t *__restrict__ stream_w, CEnt *__restrict__ tab,
                                               uint32_t tab_t_hi) {
-  const StreamBatch<TPL> bt(trace_begin, n_traces, base);
+  const StreamBatch<TPL, kHeldA> bt(c, trace_begin, n_traces, base);
   static_assert(64 * TPL < 256, "a record's 500 count is packed into a byte");
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   const uint32_t lane = lane_id();
@@ -641,7 +710,7 @@ __device__ __forceinline__ void walk_stream_cl(const Ctx &c, CNode4 *__restrict_
                                                const uint32_t *__restrict__ close_slot, CU32 *__restrict__ close_end,
                                                const uint32_t *__restrict__ stream_w, CEnt *__restrict__ tab,
                                                uint32_t tab_t_hi) {
-  const StreamBatch<TPL> bt(trace_begin, n_traces, base);
+  const StreamBatch<TPL, kHeldCl> bt(c, trace_begin, n_traces, base);
   const uint32_t lane = lane_id();
   uint32_t errh[TPL], le[TPL];
 #pragma unroll
@@ -769,7 +838,7 @@ __device__ __forceinline__ void walk_stream_mark(const Ctx &c, CNode4 *__restric
                                                  uint32_t n_nodes, uint64_t t_static, uint64_t trace_begin,
                                                  uint64_t n_traces, uint64_t base, CEnt *__restrict__ tab,
                                                  uint32_t tab_t_hi) {
-  const StreamBatch<TPL> bt(trace_begin, n_traces, base);
+  const StreamBatch<TPL, kHeldMark> bt(c, trace_begin, n_traces, base);
   const bool lane0 = lane_id() == 0;
   uint32_t errh[TPL], mk[TPL];
 #pragma unroll
