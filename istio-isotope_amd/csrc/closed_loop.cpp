@@ -2,13 +2,12 @@
 // checks of a caller's isim_closed_loop and batch, the schedule of one request
 // and the rule as a plain sequential loop.  No HIP: these work without a GPU.
 #include "closed_loop.h"
+#include "error.h"
 
 #include <string>
 #include <vector>
 
 namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-
 namespace cl {
 
 const char *client_error(const Client *cl) {

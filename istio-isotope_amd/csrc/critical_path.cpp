@@ -3,12 +3,11 @@
 // plain loop over the steps the device runs, and the merge.  No HIP: these work
 // without a GPU.
 #include "critical_path.h"
+#include "error.h"
 
 #include <string>
 
 namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-
 namespace cp {
 
 namespace {

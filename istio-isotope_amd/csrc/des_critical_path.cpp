@@ -2,13 +2,10 @@
 // §22): the sizes, the merge and the fold of a list of traces (dcp::fold_list:
 // plain loops over the phases the device runs).  No HIP: these work without a GPU.
 #include "des_critical_path.h"
+#include "error.h"
 
 #include <string>
 #include <vector>
-
-namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-}  // namespace isim
 
 namespace {
 namespace cp = isim::cp;

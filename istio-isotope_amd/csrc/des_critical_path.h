@@ -215,7 +215,7 @@ inline void fold_list(const cp::ScriptView &v, KOf kof, const uint64_t *off, uin
   }
 }
 
-// ---- host side: every check of a handler that needs no GPU (api.hip owns the handler: what
+// ---- host side: every check of a handler that needs no GPU (handler.h has the handler; des_host.hip: what
 // isim_serve_des_spans_device refuses with a tap); ISIM_OK or ISIM_EINVAL
 int check_handler(const isim_handler *h);
 

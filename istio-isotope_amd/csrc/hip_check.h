@@ -1,5 +1,5 @@
-// Error reporting of the C-ABI translation units outside api.hip: the
-// thread's message (isim_last_error) and the check of a HIP call.
+// Error reporting of the C-ABI translation units that call HIP: the thread's
+// message (error.h) and the check of a HIP call.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,10 +7,7 @@
 #include <string>
 
 #include "../../include/isim.h"
-
-namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-}
+#include "error.h"
 
 // returns ISIM_EHIP from the calling function when a HIP call fails
 #define ISIM_HIPCHK(expr)                                                                          \

@@ -28,16 +28,13 @@
 #include <vector>
 
 #include "../../include/isim.h"
-
-namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-}
+#include "error.h"
 
 static_assert(sizeof(isim_multi_id) == sizeof(ncclUniqueId), "isim_multi_id must hold an ncclUniqueId");
 
 namespace {
 
-// isim_last_error() reads api.hip's thread-local message
+// isim_last_error() reads the thread-local message behind set_error (error.h)
 int mfail(int code, const std::string &msg) { return isim::set_error(code, msg); }
 
 struct Rccl {

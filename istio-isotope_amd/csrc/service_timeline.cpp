@@ -8,11 +8,8 @@
 #include <vector>
 
 #include "des.h"
+#include "error.h"
 #include "spans.h"
-
-namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-}  // namespace isim
 
 namespace {
 namespace svt = isim::svt;

@@ -151,7 +151,7 @@ inline void fold_host(const RowArgs &a, uint32_t n_services, const uint64_t *hol
     }
 }
 
-// ---- host side: every check of a handler that needs no GPU (api.hip owns the handler: what
+// ---- host side: every check of a handler that needs no GPU (handler.h has the handler; des_host.hip: what
 // isim_serve_des_spans_device refuses with a tap); ISIM_OK or ISIM_EINVAL
 int check_handler(const isim_handler *h);
 // ... and of the parameters and the table's size (service_timeline.cpp); the cells of the table on success

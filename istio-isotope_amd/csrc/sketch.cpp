@@ -5,12 +5,9 @@
 #include <string>
 
 #include "../../include/isim.h"
+#include "error.h"
 #include "quantile_rank.h"
 #include "sketch_bucket.h"
-
-namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-}
 
 namespace {
 

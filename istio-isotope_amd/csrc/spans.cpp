@@ -3,13 +3,12 @@
 // the device runs, as tests/cpp/tree_walk_check.cpp runs it), the start times
 // and the selection as a plain loop.  No HIP: these work without a GPU.
 #include "spans.h"
+#include "error.h"
 
 #include <string>
 #include <vector>
 
 namespace isim {
-int set_error(int code, const std::string &msg);  // api.hip
-
 namespace spans {
 
 const char *handler_error(const Program &p) {

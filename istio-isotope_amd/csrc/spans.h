@@ -23,7 +23,7 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint64_t kMaxIds = 1ull << 32;
 constexpr uint64_t kMaxRecords = 1ull << 40;
 
-// ---- what the span code reads of a handler (api.hip owns the struct): its program, graph and
+// ---- what the span code reads of a handler (handler.h has the struct): its program, graph and
 // parameters, and a slot for the per-device tables of spans.hip (freed with the handler)
 struct HandlerView {
   const Program *prog;

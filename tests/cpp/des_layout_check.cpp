@@ -152,7 +152,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "plan: %s\n", err.c_str());
     return 3;
   }
-  // the C ABI's stats words and table rows (api.hip stats_words)
+  // the C ABI's stats words and table rows (handler.h stats_words)
   const uint64_t rows = prog.row_svc.size();
   const uint64_t words = ISIM_ST_SVC_DUR(prog.n_slots) + (uint64_t)ISIM_SVC_DUR_WORDS * (prog.static_walk ? 0 : rows);
   for (uint64_t n : {1ull, 255ull, 256ull, 4097ull, 5000ull})

@@ -159,6 +159,168 @@ def test_des_class():
         isim.DesHandler(d.handler, 0).serve(0, 1)
 
 
+def test_des_entry_points_refuse_on_the_host():
+    """Every argument the DES, arrivals and profile entry points refuse before any HIP call: the status and a
+    key word of the message, and which refusal comes first where two apply.  The addresses are never read."""
+    import ctypes as C
+    native = isim.native
+    lib = native.load()
+    h = _handler(tree_topology(2, 2))
+    hh = h._h
+    outside = tree_topology(2, 2)
+    outside["services"][-1].update(numReplicas=70000, script=[{"sleep": "1ms"}])
+    outside_h = _handler(outside)   # a graph outside the DES class
+    ho = outside_h._h
+    rec, st, tab, ws, big = 0x10000, 0x20000, 0x30000, 0x40000, 1 << 40
+
+    def refused(rc, word):
+        assert rc == native.EINVAL and word in native.last_error(), (rc, word, native.last_error())
+
+    def params(mean=300_000, flags=0, reserved=0):
+        return C.byref(native.DesParams(mean, flags, reserved))
+
+    def profile(segs, flags=0):
+        arr = (native.LoadSegment * len(segs))(*[native.LoadSegment(d, m) for d, m in segs])
+        lp = native.LoadProfile(arr, len(segs), flags)
+        lp._keep = arr
+        return C.byref(lp)
+
+    good, bad = profile([(1000, 5), (0, 7)]), profile([(5, 1000)])   # bad: a last segment with a duration
+    slow = profile([(0, 1 << 34)])   # its horizon passes 2^62 ns within 2^31 traces
+    bad_params = [(params(mean=0), "mean_interarrival_ns"), (params(mean=(1 << 34) + 1), "mean_interarrival_ns"),
+                  (params(flags=2), "flags"), (params(flags=0x80000001), "flags"), (params(reserved=1), "reserved")]
+
+    # isim_des_workspace_bytes
+    b = C.c_uint64()
+    refused(lib.isim_des_workspace_bytes(None, 8, C.byref(b)), "null")
+    refused(lib.isim_des_workspace_bytes(hh, 8, None), "null")
+    refused(lib.isim_des_workspace_bytes(ho, 8, C.byref(b)), "replicas")
+    assert lib.isim_des_workspace_bytes(hh, 8, C.byref(b)) == native.OK and b.value > 0
+    need = b.value
+
+    # isim_serve_des_device: no alignment check, and the workspace is sized only after the device's tables exist
+    def dev(h_=hh, p=None, n=8, s=st, t=tab):
+        return lib.isim_serve_des_device(h_, p or params(), 0, n, rec, s, t, ws, big, None)
+    refused(dev(h_=None), "null")
+    refused(lib.isim_serve_des_device(hh, None, 0, 8, rec, st, tab, ws, big, None), "null")
+    refused(dev(s=None), "null")
+    refused(dev(t=None), "null")
+    for p, word in bad_params:
+        refused(dev(p=p), word)
+        refused(dev(p=p, n=0), word)              # bad parameters are bad with nothing to do, too
+    refused(dev(n=(1 << 31) + 1), "2^31")
+    refused(dev(p=params(mean=0), n=(1 << 31) + 1), "mean_interarrival_ns")   # the parameters come first
+    assert dev(n=0) == native.OK
+    assert dev(n=0, s=st + 4, t=tab + 4) == native.OK
+    # the host twin refuses null pointers and a graph outside the class before it touches the device
+    refused(lib.isim_serve_des(None, 0, params(), 0, 8, None, None, None), "null")
+    refused(lib.isim_serve_des(hh, 0, None, 0, 8, None, None, None), "null")
+    refused(lib.isim_serve_des(ho, 0, params(), 0, 8, None, None, None), "replicas")
+
+    # isim_serve_des_profile_device
+    def pdev(h_=hh, lp=good, fl=0, n=8, r=rec, s=st, t=tab, w=ws, wb=big):
+        return lib.isim_serve_des_profile_device(h_, lp, fl, 0, n, r, s, t, w, wb, None)
+    refused(pdev(h_=None), "null")
+    refused(pdev(lp=None), "load profile")
+    refused(pdev(lp=bad), "load profile")
+    refused(pdev(lp=bad, fl=2, s=None, n=0), "load profile")    # a profile's errors come first
+    refused(pdev(fl=2), "des_flags")
+    refused(pdev(fl=2, n=(1 << 31) + 1), "des_flags")
+    refused(pdev(n=(1 << 31) + 1), "2^31")
+    refused(pdev(lp=slow, n=1 << 31), "horizon")
+    refused(pdev(lp=slow, n=1 << 31, s=None), "horizon")
+    refused(pdev(s=None), "null")
+    refused(pdev(t=None), "null")
+    refused(pdev(s=None, n=0), "null")
+    assert pdev(n=0) == native.OK
+    assert pdev(n=0, s=st + 4) == native.OK                     # nothing to do: alignment is not looked at
+    for kw in ({"s": st + 4}, {"t": tab + 4}, {"w": ws + 4}, {"r": rec + 8}):
+        refused(pdev(**kw), "aligned")
+        refused(pdev(wb=need - 1, **kw), "aligned")             # alignment before the workspace's size
+    refused(pdev(wb=need - 1), "workspace")
+    refused(pdev(wb=0), "workspace")
+    refused(pdev(w=None), "workspace")
+    assert pdev(r=None, wb=need - 1) == native.EINVAL           # no records is no misalignment
+    refused(pdev(h_=ho), "replicas")
+    refused(pdev(h_=ho, s=st + 4), "aligned")                   # the class is checked with the workspace
+    # its host twin
+    def phost(h_=hh, lp=good, n=8):
+        return lib.isim_serve_des_profile(h_, 0, lp, 0, n, None, None, None)
+    refused(phost(h_=None), "null")
+    refused(phost(lp=None), "load profile")
+    refused(phost(lp=bad), "load profile")
+    refused(phost(n=(1 << 31) + 1), "2^31")
+    refused(phost(lp=slow, n=1 << 31), "horizon")
+    refused(phost(h_=ho), "replicas")
+
+    # isim_des_arrivals_device and isim_des_arrivals
+    wsb = C.c_uint64()
+    assert lib.isim_des_arrivals_workspace_bytes(100, C.byref(wsb)) == native.OK
+    refused(lib.isim_des_arrivals_workspace_bytes(100, None), "null")
+    refused(lib.isim_des_arrivals_workspace_bytes((1 << 40) + 1, C.byref(wsb)), "2^40")
+
+    def adev(h_=hh, p=None, n=100, a=rec, w=ws, wb=wsb.value):
+        return lib.isim_des_arrivals_device(h_, p or params(), 0, n, a, w, wb, None)
+
+    def ahost(h_=hh, p=None, n=100, a=rec, **_):
+        return lib.isim_des_arrivals(h_, 0, p or params(), 0, n, a)
+    for f in (adev, ahost):
+        refused(f(h_=None), "null")
+        for p, word in bad_params:
+            refused(f(p=p), word)
+            refused(f(p=p, n=0, a=None), word)
+        refused(f(n=(1 << 40) + 1), "2^40")
+        refused(f(p=params(flags=2), n=(1 << 40) + 1), "flags")
+        refused(f(a=None), "null arrivals buffer")
+        assert f(n=0, a=None) == native.OK
+    refused(lib.isim_des_arrivals_device(hh, None, 0, 100, rec, ws, wsb.value, None), "null")
+    refused(lib.isim_des_arrivals(hh, 0, None, 0, 100, rec), "null")
+    refused(adev(w=None), "workspace")
+    refused(adev(wb=wsb.value - 1), "workspace")
+    refused(adev(wb=0, a=rec + 4), "workspace")                 # the workspace's size before alignment
+    refused(adev(a=rec + 4), "aligned")
+    refused(adev(w=ws + 4), "aligned")
+    assert adev(n=0, a=rec + 4) == native.OK
+
+    # isim_profile_arrivals_device and isim_profile_arrivals
+    assert lib.isim_profile_arrivals_workspace_bytes(100, C.byref(wsb)) == native.OK
+    refused(lib.isim_profile_arrivals_workspace_bytes(100, None), "null")
+    refused(lib.isim_profile_arrivals_workspace_bytes((1 << 32) + 1, C.byref(wsb)), "2^32")
+
+    def qdev(h_=hh, lp=good, n=100, a=rec, w=ws, wb=wsb.value):
+        return lib.isim_profile_arrivals_device(h_, lp, 0, n, a, w, wb, None)
+
+    def qhost(h_=hh, lp=good, n=100, a=rec, **_):
+        return lib.isim_profile_arrivals(h_, 0, lp, 0, n, a)
+    for f in (qdev, qhost):
+        refused(f(h_=None), "null")
+        refused(f(lp=None), "load profile")
+        refused(f(lp=bad), "load profile")
+        refused(f(lp=bad, n=0, a=None), "load profile")
+        refused(f(lp=bad, n=(1 << 32) + 1), "load profile")
+        refused(f(n=(1 << 32) + 1), "2^32")
+        refused(f(a=None), "null arrivals buffer")
+        refused(f(lp=slow, n=1 << 32), "horizon")
+        refused(f(lp=slow, n=1 << 32, a=None), "null arrivals buffer")   # the buffer before the horizon
+        assert f(n=0, a=None) == native.OK
+    refused(qdev(w=None), "workspace")
+    refused(qdev(wb=wsb.value - 1), "workspace")
+    refused(qdev(wb=0, a=rec + 4), "workspace")
+    refused(qdev(a=rec + 4), "aligned")
+    refused(qdev(w=ws + 4), "aligned")
+
+    # isim_serve_des_spans_device without a tap is the call it stands for, whatever that checks
+    def sdev(p=None, lp=None, n=8, s=st, wb=big):
+        return lib.isim_serve_des_spans_device(hh, p or params(), lp, 0, n, rec, s, tab, ws, wb, None, None)
+    refused(sdev(p=params(mean=0)), "mean_interarrival_ns")
+    refused(sdev(n=(1 << 31) + 1), "2^31")
+    refused(sdev(lp=bad), "load profile")
+    refused(sdev(lp=good, s=st + 4), "aligned")
+    refused(sdev(lp=good, wb=need - 1), "workspace")
+    refused(sdev(lp=good, p=params(flags=2)), "des_flags")
+    assert sdev(lp=good, p=params(mean=0, reserved=1), n=0) == native.OK   # with a profile only the flags are read
+
+
 def _binary_dag(depth):
     """s_i calls s_{i+1} twice, in two sequential call steps: 2^(depth+1) - 1
     invocations per trace, and every step begin waits for the previous step's

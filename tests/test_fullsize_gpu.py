@@ -60,7 +60,7 @@ def _launch_edge_windows(case: Case, rec, begin, n, launches, width=256):
     """Oracle windows at the first and last `width` traces of every launch and
     straddling every internal split of a launch (the library splits a batch
     into launches of at most max_launch_traces traces so that no u32 LDS
-    counter can wrap: api.hip launch_walk, Program::tree_mult)."""
+    counter can wrap: walk_host.hip launch_walk, Program::tree_mult)."""
     m = int(case.handler.launch_info(0)["max_launch_traces"])
     assert m >= 1
     edges = set()
