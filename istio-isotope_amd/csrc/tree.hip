@@ -18,7 +18,7 @@
 // Statistics (isim.h stats words):
 //   * per-slot executed calls / callee 500s: u32 LDS counters, one LDS
 //     atomic per event, flushed once per workgroup (launches are split so a
-//     counter cannot wrap: api.hip launch_walk, Program::tree_mult);
+//     counter cannot wrap: walk_host.hip launch_walk, Program::tree_mult);
 //   * per-service durations (RecordResponseSent, prometheus/handler.go:101-106):
 //     code-200 sums in u64 LDS words; code-500 sums by global atomics (500s
 //     are rare); bucket counts of a row whose duration bucket is static (the
@@ -435,7 +435,7 @@ __global__ void __launch_bounds__(kWgThreads, WPE)
     L.sp_stride = kp.spill_lanes;
   }
   bool active = false;  // the lane holds a trace whose record is not yet written
-  uint32_t idx = 0;     // launches hold fewer than 2^31 traces (api.hip max_launch_traces)
+  uint32_t idx = 0;     // launches hold fewer than 2^31 traces (walk_host.hip max_launch_traces)
   // per-lane sums in 32 bits (a latency sum that wraps carries 2^32 into the
   // workgroup's u64 accumulator at once); trace and 500 counts follow from
   // the histograms at the flush

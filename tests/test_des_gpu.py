@@ -29,8 +29,8 @@ class DesCase:
         self.og = oc.OracleGraph(self.sg, self.op)
         self.mean = mean_ns
 
-    def compare(self, begin, n, records=True):
-        recs, stats, table = self.d.serve(begin, n, device=0, records=records)
+    def compare(self, begin, n, records=True, wide=False):
+        recs, stats, table = self.d.serve(begin, n, device=0, records=records, wide=wide)
         orec, ost, odes = od.run(self.sg, self.op, self.sg.entry(), begin, n, self.mean, records=records, og=self.og)
         if records:
             assert_records_equal(recs, orec)
@@ -75,6 +75,23 @@ def test_ragged_batches(gpu, n):
 @pytest.mark.parametrize("reps", [2, 5, 64])
 def test_leaf_replicas(gpu, reps):
     DesCase(_sleepy_tree(3, 4, reps), 700_000).compare(0, 12000)
+
+
+# the replicated queue pass (des_down, one workgroup per position) in its four
+# forms: a service with 3 replicas as a leaf (its finish fused into the queue
+# pass) and as a caller, narrow and wide rows; 4097 traces are whole
+# 1,024-trace chunks and a one-trace tail
+@pytest.mark.parametrize("wide", [False, True])
+@pytest.mark.parametrize("where", ["leaf", "caller"])
+def test_replicated_queue_rows(gpu, where, wide):
+    doc = _sleepy_tree(3, 3)
+    for s in doc["services"]:
+        is_leaf = not any(isinstance(x, list) for x in s["script"])
+        if is_leaf == (where == "leaf"):
+            s["numReplicas"] = 3
+            s["errorRate"] = 0.05
+    _, stats, _ = DesCase(doc, 3_000_000).compare(0, 4097, wide=wide)  # latencies well below 2^31 ns
+    assert stats[isim.native.ST_DES_RETRY] == 0  # narrow rows stayed narrow
 
 
 def test_error_rate_extremes(gpu):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build a libisim variant with one HIP source recompiled under extra flags:
 #   tools/build_variant.sh <out name> <source.hip> <flags...>
-# e.g. tools/build_variant.sh libisim_hoist.so des.hip -DDES_HOIST_500
+# e.g. tools/build_variant.sh libisim_up3.so des.hip -DISIM_DES_UP_CB=3
 # (run `make -C istio-isotope_amd/csrc` first: the other objects are reused)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
