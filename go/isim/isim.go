@@ -155,6 +155,30 @@ func (h *Handler) LastDesBatch() (DesBatch, error) {
 	return DesBatch{uint32(st.passes), uint32(st.syncs), uint64(st.items)}, nil
 }
 
+// SetDesWorkers sets the workers per replica of every service, by service
+// index (isim_des_workers_set): 1 .. 65536 each, behind the replica's one FIFO
+// queue.  nil resets every service to 1.  Handler state, read at the start of
+// each DES batch; not to be changed while one is in flight.  More than one
+// worker needs the item engine (ISIM_FLAG_DYNAMIC) and an acyclic call-step
+// schedule.
+func (h *Handler) SetDesWorkers(workers []uint32) error {
+	var wp *C.uint32_t
+	if len(workers) > 0 {
+		wp = (*C.uint32_t)(unsafe.Pointer(&workers[0]))
+	}
+	return lastErr(C.isim_des_workers_set(h.h, wp, C.uint32_t(len(workers))))
+}
+
+// DesWorkers returns the workers per replica of the nServices services
+// (isim_des_workers_get): 1 each until set.
+func (h *Handler) DesWorkers(nServices int) ([]uint32, error) {
+	w := make([]uint32, nServices+1)
+	if err := lastErr(C.isim_des_workers_get(h.h, (*C.uint32_t)(unsafe.Pointer(&w[0])))); err != nil {
+		return nil, err
+	}
+	return w[:nServices], nil
+}
+
 // Quantiles is one class's exact latency percentiles (isim_latency_quantiles):
 // the records in the class and, per requested quantile, the nearest-rank
 // latency in ns (all 0 for an empty class).
@@ -490,7 +514,8 @@ func svtParams(t0Ns, windowNs uint64, nWindows uint32) C.isim_timeline_params {
 }
 
 // ServiceHolds returns per service its worker hold in ns and its replicas
-// (isim_des_service_holds): BusyNs / (window x replicas) is the utilisation.
+// (isim_des_service_holds): BusyNs / (window x replicas x workers) is the
+// utilisation (DesWorkers: 1 each unless set).
 func (h *Handler) ServiceHolds(nServices int) ([]uint64, []uint32, error) {
 	hold, reps := make([]uint64, nServices+1), make([]uint32, nServices+1)
 	rc := C.isim_des_service_holds(h.h, u64ptr(hold), (*C.uint32_t)(unsafe.Pointer(&reps[0])))

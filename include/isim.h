@@ -331,7 +331,8 @@ ISIM_API int isim_stats_fold_durations(const isim_handler *h, const uint64_t *st
 /* ---- per-replica worker-pool DES (BASELINE config 5) ----
  * Open-loop Poisson arrivals of the client requests at the entry; every
  * replica of a service (svc.Service.NumReplicas, convert/pkg/graph/svc/
- * service.go:30-31) is a FIFO queue in front of ONE worker, held for the
+ * service.go:30-31) is a FIFO queue in front of ONE worker (or of W_s workers:
+ * isim_des_workers_set below), held for the
  * invocation's sleep total; an invocation's script (Handler.ServeHTTP,
  * handler.go:37-79) starts when the worker takes it.  Statuses, hops and
  * call counters are those of the walk; latencies and the per-service
@@ -387,6 +388,26 @@ typedef struct {
   uint64_t items;
 } isim_des_batch_stats;
 ISIM_API int isim_des_last_batch(const isim_handler *h, isim_des_batch_stats *out);
+/* Worker pools (EXT): service s has W_s workers per
+ * replica, 1 .. 65536, default 1, behind the replica's one FIFO queue.  Within
+ * a replica the requests are ordered (arrival, trace, hop) as ever, and the
+ * request of rank j (0-based, per replica, per batch) starts at
+ *   S_j = max(a_j, S_{j - W_s} + P_s),   S_j = a_j for j < W_s,
+ * P_s the service's worker hold; everything else of the DES is unchanged, and
+ * with every W_s = 1 this is the one-worker rule.  workers[n_services], by
+ * service index; NULL resets every service to 1.  Handler state: read at the
+ * start of each DES batch of the handler (isim_serve_des*,
+ * isim_serve_des_profile*, isim_serve_des_spans*, and through the spans the
+ * DES critical path and the service timeline), not to be changed while one is
+ * in flight.  A handler whose workers are all 1, set or never set, runs the
+ * launches it always ran.  ISIM_EINVAL, before any HIP call: a count of 0 or
+ * above 65536; n_services not the graph's; any count above 1 on a handler
+ * whose DES runs on the static engine (isim_des_info.items == 0: create it
+ * with ISIM_FLAG_DYNAMIC) or whose call-step schedule is cyclic
+ * (isim_des_info.cyclic: not built). */
+ISIM_API int isim_des_workers_set(isim_handler *h, const uint32_t *workers, uint32_t n_services);
+/* host only, no GPU: the handler's workers per service, [n_services] (1 each until set) */
+ISIM_API int isim_des_workers_get(const isim_handler *h, uint32_t *workers);
 /* Device workspace a batch of n_traces needs (either row width: 8 B per invocation per trace + ~40 B per trace). */
 ISIM_API int isim_des_workspace_bytes(const isim_handler *h, uint64_t n_traces, uint64_t *bytes);
 /* One DES batch (trace ids [trace_begin, trace_begin+n_traces), arrivals from
@@ -1220,7 +1241,7 @@ ISIM_API int isim_des_critical_path(int device, const isim_handler *h, const uin
  * the host and the device refuse the same spans.
  *
  * Derived: the mean queue length of a window is QUEUED_NS / window_ns, the
- * utilisation BUSY_NS / (window_ns x replicas), the queue depth at the end of
+ * utilisation BUSY_NS / (window_ns x replicas x workers, isim_des_workers_get), the queue depth at the end of
  * row r the cumulative ARRIVED - STARTED over the rows <= r. */
 #define ISIM_SVT_ARRIVED   0   /* spans of s whose a falls in the row */
 #define ISIM_SVT_STARTED   1   /* spans whose S falls in it */

@@ -20,6 +20,7 @@ namespace isim {
 
 constexpr uint32_t kDesNoParent = 0xFFFFFFFFu;
 constexpr uint32_t kDesMaxReplicas = 64;  // per-replica carries of a leaf position live in LDS
+constexpr uint32_t kDesMaxWorkers = 65536; // workers per replica (isim_des_workers_set)
 constexpr uint32_t kDesMaxRounds = 65536; // schedule length limit (each round is a few launches per batch)
 constexpr uint32_t kDesFlagAlways = 1u;   // errorRate 1
 constexpr uint32_t kDesFlagLeaf = 2u;     // no call step
@@ -275,6 +276,9 @@ struct DesItemsLaunch {
   const isim_des_tap *tap;
   const uint32_t *d_slot_callee;
   uint32_t entry_service, n_services;
+  // worker pools: per duration-table row the workers of each replica of its service,
+  // on the host (null: one each, the engine's launches as they were)
+  const uint32_t *row_workers;
 };
 uint64_t des_items_workspace_bytes(uint64_t n);
 int des_items_launch(const DesItemsLaunch &L, void *stream, std::string &err);

@@ -156,6 +156,17 @@ int serve_des_device(isim_handler *h, const DesLoad &load, uint64_t trace_begin,
     L.n_slots = (uint32_t)h->prog.n_slots;
     L.flags = h->params.flags;
     L.pool = t.pool.get();
+    // the workers of this batch (handler state, read here once): per duration-table row; none set, or all 1,
+    // is the engine without pools
+    std::vector<uint32_t> row_workers;
+    {
+      std::lock_guard<std::mutex> lk(h->mu);
+      if (std::any_of(h->des_workers.begin(), h->des_workers.end(), [](uint32_t w) { return w > 1; })) {
+        row_workers.resize(h->prog.row_svc.size());
+        for (size_t r = 0; r < row_workers.size(); ++r) row_workers[r] = h->des_workers[h->prog.row_svc[r]];
+      }
+    }
+    L.row_workers = row_workers.empty() ? nullptr : row_workers.data();
     isim::DesItemsReport rep{};
     L.report = &rep;
     if (load.tap) {  // the slot-to-callee table of the span code (uploaded once per handler and device)
@@ -436,6 +447,47 @@ int isim_des_info_get(const isim_handler *h, isim_des_info *out) {
   out->row_reads = (int32_t)rr;
   out->row_writes = (int32_t)rw;
   out->items = h->des.items ? 1 : 0;
+  return ISIM_OK;
+}
+
+// ---- worker pools: host state, every check before any HIP call
+int isim_des_workers_set(isim_handler *h, const uint32_t *workers, uint32_t n_services) {
+  if (!h) return set_error(ISIM_EINVAL, "DES workers: null handler");
+  if (!workers) {  // every service back to one worker
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->des_workers.clear();
+    return ISIM_OK;
+  }
+  if (n_services != (uint32_t)h->prog.n_services)
+    return set_error(ISIM_EINVAL, "DES workers: n_services is " + std::to_string(n_services) + ", the graph has " +
+                                      std::to_string(h->prog.n_services) + " services");
+  bool pooled = false;
+  for (uint32_t s = 0; s < n_services; ++s) {
+    if (workers[s] == 0 || workers[s] > isim::kDesMaxWorkers)
+      return set_error(ISIM_EINVAL, "DES workers: service " + std::to_string(s) + " has " + std::to_string(workers[s]) +
+                                        " workers, outside 1 .. 65536");
+    pooled = pooled || workers[s] > 1;
+  }
+  if (pooled) {
+    if (const int drc = des_ensure(h)) return drc;
+    if (!h->des.items)
+      return set_error(ISIM_EINVAL, "DES workers: more than one worker per replica needs the item engine, and this "
+                                    "handler's DES runs on the static engine: create the handler with "
+                                    "ISIM_FLAG_DYNAMIC");
+    if (h->des.cyclic)
+      return set_error(ISIM_EINVAL, "DES workers: more than one worker per replica on a cyclic call-step schedule "
+                                    "(isim_des_info.cyclic) is not built");
+  }
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->des_workers.assign(workers, workers + n_services);
+  return ISIM_OK;
+}
+
+int isim_des_workers_get(const isim_handler *h, uint32_t *workers) {
+  if (!h || !workers) return set_error(ISIM_EINVAL, "DES workers: null argument");
+  isim_handler *hm = const_cast<isim_handler *>(h);
+  std::lock_guard<std::mutex> lk(hm->mu);
+  for (int32_t s = 0; s < h->prog.n_services; ++s) workers[s] = h->des_workers.empty() ? 1u : h->des_workers[s];
   return ISIM_OK;
 }
 

@@ -28,7 +28,9 @@
 //                  row | replica | arrival — two when the bits do not fit —,
 //                  ties in (trace, hop) order as the oracle's event heap pops
 //                  them — then one segmented max-plus scan: S = max(a,
-//                  S_prev + hold)), finishes (deepest group first: F from the
+//                  S_prev + hold); a service with W workers per replica: the
+//                  order refined first into each replica's W rank classes,
+//                  one such queue each, des_workers.h), finishes (deepest group first: F from the
 //                  start or last BK and the callees' maxima, which each callee
 //                  folds into its caller's per-step slot with a 64-bit atomic
 //                  max); statistics summed in LDS per 4,096-item chunk; a
@@ -1199,6 +1201,9 @@ __global__ void __launch_bounds__(kT) k_qscan(K k, uint64_t m, QSrc q, QState *q
   }
 }
 
+// ---- 4b''. worker pools: a pooled round's order refined into rank classes
+#include "des_workers.h"
+
 // ---- 4c. finishes of one group (its items position by position): per
 // item the finish and its callee maximum into the caller's slot; the
 // statistics summed over a thread's run of one position (and one bucket for
@@ -1606,6 +1611,10 @@ struct Batch {
   ItemDims dims{};
   uint64_t M = 0;
   std::vector<uint64_t> row_hold;  // per duration-table row: the service's worker hold
+  // worker pools (des_workers.h): per row its workers when some row has more than one (else empty), and per
+  // round whether a pooled row queues in it
+  std::vector<uint32_t> row_workers;
+  std::vector<uint8_t> round_pooled;
   uint32_t rep_bits = 0, row_bits = 0;
   bool qscan = false, two_sorts = false, keep_ord = false;
   uint32_t qepoch = 0, qtbase = 0;  // k_qscan launches (the states' epochs: 1, 2, ...) and tickets taken
@@ -1684,6 +1693,12 @@ struct Batch {
     row_bits = bits_for(max_row);
     row_hold.assign((size_t)max_row + 1, 0);
     for (const DesPos &q : pl.pos) row_hold[q.row] = q.hold;
+    round_pooled.assign(R, 0);
+    if (L.row_workers && std::any_of(L.row_workers, L.row_workers + row_hold.size(), [](uint32_t w) { return w > 1; })) {
+      row_workers.assign(L.row_workers, L.row_workers + row_hold.size());
+      for (size_t v = 0; v < pl.pos.size(); ++v)
+        if (row_workers[pl.pos[v].row] > 1) round_pooled[pl.item_pos[v].qround] = 1;
+    }
     // ISIM_FLAG_DES_TWO_SORTS: always the two-sort queue path; ISIM_FLAG_DES_SORT_ALL:
     // never reuse a kept order (independent checks)
     two_sorts = (L.flags & ISIM_FLAG_DES_TWO_SORTS) != 0;
@@ -1753,6 +1768,8 @@ struct Batch {
 
   // the per-item arrays and the rounds' sort buffers, one allocation (des_items_layout)
   int allocate() {
+    // (isim_des_workers_set refuses them; their kept orders and quiet passes know no rank classes)
+    if (!row_workers.empty() && pl.cyclic) return fail("worker pools on a cyclic schedule");
     size_t sort32_bytes = 0, sort64_bytes = 0, sbk_bytes = 0, sop_bytes = 0, perm_bytes = 0;
     (void)rocprim::radix_sort_pairs(nullptr, sort32_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
                                     (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)M, 0, 32);
@@ -1769,7 +1786,8 @@ struct Batch {
                                     (uint32_t *)nullptr, rocprim::make_counting_iterator<uint32_t>(0u),
                                     (uint32_t *)nullptr, (size_t)M, 0, 32);
     tmp_bytes = std::max({sort32_bytes, sort64_bytes, sbk_bytes, sop_bytes, perm_bytes});
-    dims = ItemDims{M, n, k.aw, k.bw, R, row_hold.size(), pl.pos.size(), pl.cyclic, pl.modeb, tmp_bytes, k.cshift};
+    dims = ItemDims{M, n, k.aw, k.bw, R, row_hold.size(), pl.pos.size(), pl.cyclic, pl.modeb, tmp_bytes, k.cshift,
+                    !row_workers.empty()};
     Arena sizing;
     des_items_layout(sizing, B, dims);
     if (!pool_alloc(item_mem, sizing.bytes())) return fail("item allocation");
@@ -1840,6 +1858,9 @@ struct Batch {
     if (hipMemcpyAsync(B.d_row_hold, row_hold.data(), row_hold.size() * 8, hipMemcpyHostToDevice, s) != hipSuccess)
       return fail("hold table upload");
     k.row_hold = B.d_row_hold;
+    if (!row_workers.empty() && hipMemcpyAsync(B.d_row_workers, row_workers.data(), row_workers.size() * 4,
+                                               hipMemcpyHostToDevice, s) != hipSuccess)
+      return fail("worker table upload");
     // the step-begin ops; each position's item range (k.ipos is sorted)
     hipLaunchKernelGGL(k_bucket_keys, dim3(grid_for(M)), dim3(kT), 0, s, k, B.op_k, B.op_v, B.ovf + 3);
     const uint32_t NP = (uint32_t)pl.pos.size();
@@ -1899,7 +1920,11 @@ struct Batch {
     // (a no-sort round reads no arrival range back; k_qscan computes its arrivals)
     uint64_t *slot = B.mm + 4 * (qn & 1u), *slot_next = B.mm + 4 * ((qn + 1) & 1u);
     const bool chk = !nosort && have_ord[r];
-    if (!(nosort && qscan)) {
+    // a pooled round (des_workers.h) builds k_pairs*'s arrays whatever scans them: they are what it refines;
+    // `direct`: k_qscan reads the round's order itself
+    const bool pooled = round_pooled[r] != 0;
+    const bool direct = qscan && !pooled;
+    if (!(nosort && direct)) {
       ++qn;
       hipLaunchKernelGGL(k_qarr, dim3(grid_for(m)), dim3(kT), 0, s, kk, list, m, (unsigned long long *)slot,
                          (unsigned long long *)slot_next);
@@ -1934,12 +1959,12 @@ struct Batch {
     int qsk = kQArrays;
     if (chk && !bad) {  // the kept order holds: no sort
       qsk = kQKept;
-      if (!qscan)
+      if (!direct)
         hipLaunchKernelGGL(k_pairs1o, dim3(grid_for(m)), dim3(kT), 0, s, kk, m, (const uint32_t *)ord,
                            (const uint32_t *)list, rep_bits, B.rk_a, B.rk_b, B.mp_in, B.sid);
     } else if (nosort) {
       qsk = kQList;
-      if (!qscan)  // k_qscan reads the list itself
+      if (!direct)  // k_qscan reads the list itself
         hipLaunchKernelGGL(k_pairs0, dim3(grid_for(m)), dim3(kT), 0, s, kk, list, m, B.rk_a, B.rk_b, B.mp_in, B.sid);
     } else if (!two_sorts && row_bits + rep_bits + ab <= 64) {
       hipLaunchKernelGGL(k_qkey1, dim3(grid_for(m)), dim3(kT), 0, s, kk, list, m, hmm[0], rep_bits, ab, B.key_a,
@@ -1955,7 +1980,7 @@ struct Batch {
         have_ord[r] = 1;
       }
       qsk = kQSorted;
-      if (!qscan)
+      if (!direct)
         hipLaunchKernelGGL(k_pairs1, dim3(grid_for(m)), dim3(kT), 0, s, kk, m, B.key_b, B.val_b,
                            (const uint32_t *)list, rep_bits, ab, hmm[0], B.rk_a, B.rk_b, B.mp_in, B.sid);
     } else {
@@ -1973,6 +1998,22 @@ struct Batch {
       hipLaunchKernelGGL(k_pairs2, dim3(grid_for(m)), dim3(kT), 0, s, kk, m, B.rk_b, B.rv_b, B.key_b, B.val_b, rep_bits,
                          B.rk_a, B.mp_in, B.sid);
     }
+    const uint32_t *seg_keys = B.rk_a, *seg_rows = B.rk_b, *seg_items = B.sid;
+    const MP *seg_maps = B.mp_in;
+    if (pooled) {  // the order refined: every (row, replica) segment as its rank classes, each a segment
+      const uint32_t wt = (uint32_t)((m + kWkTile - 1) / kWkTile);
+      hipLaunchKernelGGL(k_wk_tile, dim3(wt), dim3(kT), 0, s, (const uint32_t *)B.rk_a, m, B.wk_tile);
+      hipLaunchKernelGGL(k_wk_carry, dim3(1), dim3(kT), 0, s, B.wk_tile, wt);
+      hipLaunchKernelGGL(k_wk_rank, dim3(wt), dim3(kT), 0, s, (const uint32_t *)B.rk_a, m,
+                         (const uint32_t *)B.wk_tile, B.wk_start, B.wk_len);
+      hipLaunchKernelGGL(k_wk_scatter, dim3(grid_for(m)), dim3(kT), 0, s,
+                         WkArrays{B.rk_a, B.rk_b, B.sid, B.mp_in, B.wk_start, B.wk_len, B.d_row_workers, B.wk_seg,
+                                  B.wk_row, B.wk_sid, B.wk_mp},
+                         m);
+      seg_keys = B.wk_seg, seg_rows = B.wk_row, seg_items = B.wk_sid, seg_maps = B.wk_mp;
+      qsrc.segk = seg_keys, qsrc.rowk = seg_rows, qsrc.sid = seg_items, qsrc.mp = seg_maps;
+      qsk = kQArrays;
+    }
     if (qscan) {
       // 8 items per lane on a large round, 2 otherwise (more tiles to spread)
       const bool big = m >= 2048ull * 512;
@@ -1989,11 +2030,11 @@ struct Batch {
       qtbase += tiles;
     } else {
       tb = tmp_bytes;
-      if (rocprim::inclusive_scan_by_key(B.tmp, tb, B.rk_a, B.mp_in, B.mp_out, (size_t)m, MPThen(),
+      if (rocprim::inclusive_scan_by_key(B.tmp, tb, seg_keys, seg_maps, B.mp_out, (size_t)m, MPThen(),
                                          rocprim::equal_to<uint32_t>(), s) != hipSuccess)
         return fail("queue scan");
-      hipLaunchKernelGGL(k_qout, dim3(grid_for((m + span - 1) / span)), dim3(kT), 0, s, kk, m, B.rk_b, B.sid, B.mp_in,
-                         B.mp_out, span);
+      hipLaunchKernelGGL(k_qout, dim3(grid_for((m + span - 1) / span)), dim3(kT), 0, s, kk, m, seg_rows, seg_items,
+                         seg_maps, B.mp_out, span);
     }
     return 0;
   }

@@ -85,6 +85,7 @@ struct alignas(16) ItemRec {
   uint32_t x, y, z, w;
 };
 constexpr uint32_t kQTile = 512;  // items of k_qscan's smaller tile: the most states a batch needs
+constexpr uint32_t kWkTile = 1024; // items of a tile of the worker pools' head-flag scan (des_workers.h)
 }  // namespace dit
 
 // the caller's per-trace workspace (isim_des_workspace_bytes)
@@ -114,6 +115,7 @@ struct ItemDims {
   uint64_t tmp_bytes;        // the largest rocPRIM temporary storage of the batch
   uint32_t chunk_shift;      // the incremental quiet passes' trace chunks: 2^chunk_shift traces
   uint64_t n_chunks() const { return (n >> chunk_shift) + 1; }
+  bool pooled = false;       // some service has more than one worker per replica (des_workers.h)
 };
 struct ItemBufs {
   // per item (after the renumbering: position-major)
@@ -146,6 +148,11 @@ struct ItemBufs {
   void *tmp;                       // rocPRIM temporary storage
   uint8_t *chg_a, *chg_b;          // the two chunk-change maps
   uint8_t *chg_ta, *chg_tb;        // the two per-trace change maps
+  // worker pools (des_workers.h; null unless ItemDims::pooled): per row its workers; a pooled round's
+  // segment starts and lengths, the tiles' last segment starts, and the round's order refined into rank
+  // classes: segment keys, rows, items, maps
+  uint32_t *d_row_workers, *wk_start, *wk_len, *wk_tile, *wk_seg, *wk_row, *wk_sid;
+  dit::MP *wk_mp;
 };
 inline void des_items_layout(Arena &a, ItemBufs &b, const ItemDims &d) {
   const uint64_t M = d.M, ops = M * d.bw, kept = d.cyclic ? M : 0;
@@ -178,6 +185,15 @@ inline void des_items_layout(Arena &a, ItemBufs &b, const ItemDims &d) {
   b.tmp = a.take<char>(d.tmp_bytes);
   for (uint8_t **p : {&b.chg_a, &b.chg_b}) *p = a.take<uint8_t>(d.n_chunks());
   for (uint8_t **p : {&b.chg_ta, &b.chg_tb}) *p = a.take<uint8_t>(d.n + 1);
+  // worker pools: nothing unless some service has more than one worker
+  // (not even an empty part: the allocation is the same to the byte)
+  b.d_row_workers = b.wk_start = b.wk_len = b.wk_seg = b.wk_row = b.wk_sid = b.wk_tile = nullptr;
+  b.wk_mp = nullptr;
+  if (!d.pooled) return;
+  b.d_row_workers = a.take<uint32_t>(d.rows_n);
+  for (uint32_t **p : {&b.wk_start, &b.wk_len, &b.wk_seg, &b.wk_row, &b.wk_sid}) *p = a.take<uint32_t>(M);
+  b.wk_tile = a.take<uint32_t>((M + dit::kWkTile - 1) / dit::kWkTile + 1);
+  b.wk_mp = a.take<dit::MP>(M);
 }
 
 }  // namespace isim

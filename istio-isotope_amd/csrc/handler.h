@@ -11,6 +11,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/isim.h"
 #include "des.h"
@@ -119,6 +120,7 @@ struct isim_handler {
   int des_rc = ISIM_OK;
   std::string des_err;
   isim::DesPlan des;
+  std::vector<uint32_t> des_workers;  // per service, workers per replica (isim_des_workers_set); empty: one each
   std::mutex report_mu;
   isim::DesItemsReport des_report{};  // the item engine's last batch (isim_des_last_batch)
   std::mutex span_mu;

@@ -8,7 +8,8 @@
 The simulated counterpart of isotope under load: the client (Fortio's
 open-loop mode) issues requests at exponential gaps; each replica of a
 service (numReplicas, convert/pkg/graph/svc/service.go:30-31) is a FIFO queue
-in front of one worker.  Statuses/hops/counters are the static walk's;
+in front of one worker, or of ``workers`` of them (the
+requests a server handles at once).  Statuses/hops/counters are the static walk's;
 latencies and per-service durations include queueing.  Runs on the GPU
 through libisim (isim_serve_des*); graphs outside the DES class raise
 IsimError(EINVAL) with the reason.
@@ -30,9 +31,14 @@ from .sim import REC_DTYPE, Handler
 
 
 class DesHandler:
-    def __init__(self, handler: Handler, mean_interarrival_ns: int = None, profile=None):
+    def __init__(self, handler: Handler, mean_interarrival_ns: int = None, profile=None, workers=None):
         """Exactly one of mean_interarrival_ns (a stationary Poisson load) and
-        profile (an isim.LoadProfile) is given."""
+        profile (an isim.LoadProfile) is given.  workers (DESIGN.md
+        §10.1a): the workers of each replica behind its one queue — an int for
+        every service, a {service name: k} dict (the others 1) or an array by
+        service index; None leaves the handler's as they are (1 each until
+        set).  They are the HANDLER's state (isim_des_workers_set): every
+        DesHandler over it serves with them."""
         if (mean_interarrival_ns is None) == (profile is None):
             raise ValueError("DesHandler takes exactly one of mean_interarrival_ns and profile")
         self.handler = handler
@@ -41,6 +47,35 @@ class DesHandler:
         info = native.DesInfo()
         native.check(native.load().isim_des_info_get(handler._h, C.byref(info)))
         self.info = info
+        if workers is not None:
+            self.workers = workers
+
+    @property
+    def workers(self) -> np.ndarray:
+        """isim_des_workers_get: u32[n_services], the workers per replica of each service."""
+        out = np.zeros(int(self.handler.info.n_services), np.uint32)
+        native.check(native.load().isim_des_workers_get(self.handler._h, out.ctypes.data))
+        return out
+
+    @workers.setter
+    def workers(self, workers) -> None:
+        n = int(self.handler.info.n_services)
+        if workers is None:
+            native.check(native.load().isim_des_workers_set(self.handler._h, None, n))
+            return
+        if isinstance(workers, dict):
+            names = [s["name"] for s in self.handler.graph.canonical()["services"]]
+            unknown = sorted(set(workers) - set(names))
+            if unknown:
+                raise ValueError(f"workers: no service named {unknown[0]!r}")
+            workers = [workers.get(name, 1) for name in names]
+        elif np.ndim(workers) == 0:
+            workers = [workers] * n
+        vals = [int(w) for w in workers]
+        if any(w < 0 or w > 0xFFFFFFFF for w in vals):
+            raise ValueError("workers: a count outside u32")
+        w = np.ascontiguousarray(vals, dtype=np.uint32)
+        native.check(native.load().isim_des_workers_set(self.handler._h, w.ctypes.data if len(w) else None, len(w)))
 
     def last_batch(self) -> dict:
         """isim_des_last_batch: the item engine's last batch on this handler

@@ -34,6 +34,13 @@ def service_holds(handler):
     return hold, reps
 
 
+def service_workers(handler) -> np.ndarray:
+    """isim_des_workers_get: workers per replica u32[n_services] (1 each until set)."""
+    w = np.zeros(int(handler.info.n_services), np.uint32)
+    native.check(native.load().isim_des_workers_get(handler._h, w.ctypes.data))
+    return w
+
+
 def service_timeline_table_words(handler, window_ns: int, n_windows: int, t0_ns: int = 0) -> int:
     b = C.c_uint64()
     native.check(native.load().isim_service_timeline_table_words(
@@ -99,6 +106,7 @@ class ServiceTimeline:
         self.flat = np.zeros(words, np.uint64) if table is None else np.ascontiguousarray(table, dtype=np.uint64).ravel()
         assert self.flat.size == words
         self.hold_ns, self.replicas = service_holds(handler)
+        self.workers = service_workers(handler)   # as the handler has them now: those of the batches folded
 
     @property
     def table(self) -> np.ndarray:
@@ -111,9 +119,10 @@ class ServiceTimeline:
         return dict(folded=int(h[native.SVT_H_FOLDED]), refused=int(h[native.SVT_H_REFUSED]))
 
     def utilisation(self) -> np.ndarray:
-        """[n_services][n_windows] floats: BUSY_NS / (window_ns x replicas)."""
+        """[n_services][n_windows] floats: BUSY_NS / (window_ns x replicas x workers)."""
         busy = self.table[:, 1:-1, native.SVT_BUSY_NS].astype(np.float64)
-        return busy / (float(self.window_ns) * self.replicas.astype(np.float64)[:, None])
+        servers = self.replicas.astype(np.float64) * self.workers.astype(np.float64)
+        return busy / (float(self.window_ns) * servers[:, None])
 
     def mean_queue(self) -> np.ndarray:
         """[n_services][n_windows] floats: the mean queue length QUEUED_NS / window_ns."""
@@ -137,9 +146,10 @@ class ServiceTimeline:
     def to_text(self, top: int = None) -> str:
         """The busiest services (by worker-busy time over all rows) with their peak-utilisation window."""
         h, t = self.header, self.table
+        pooled = bool((self.workers > 1).any())   # the workers column only when some service has a pool
         lines = [f"service timeline of {h['folded']} spans: {self.n_windows} windows of {self.window_ns} ns from "
                  f"{self.t0_ns} ns" + (f", {h['refused']} refused" if h["refused"] else ""),
-                 f"{'service':<24}{'replicas':>9}{'busy_ns':>16}{'peak util':>10}{'at window':>10}{'peak queue':>11}"
+                 f"{'service':<24}{'replicas':>9}" + (f"{'workers':>8}" if pooled else "") + f"{'busy_ns':>16}{'peak util':>10}{'at window':>10}{'peak queue':>11}"
                  f"{'max_wait_ns':>14}{'invocations':>12}"]
         util, queue = self.utilisation(), self.mean_queue()
         busy = t[:, :, native.SVT_BUSY_NS].sum(axis=1, dtype=np.uint64)
@@ -147,7 +157,8 @@ class ServiceTimeline:
                  if int(t[s, :, native.SVT_ARRIVED].sum())]
         for s in order[:top]:
             w = int(np.argmax(util[s]))
-            lines.append(f"{self.names[s]:<24}{int(self.replicas[s]):>9}{int(busy[s]):>16}{util[s, w]:>10.3f}{w:>10}"
+            lines.append(f"{self.names[s]:<24}{int(self.replicas[s]):>9}"
+                         + (f"{int(self.workers[s]):>8}" if pooled else "") + f"{int(busy[s]):>16}{util[s, w]:>10.3f}{w:>10}"
                          f"{queue[s].max():>11.2f}{int(t[s, :, native.SVT_MAX_WAIT].max()):>14}"
                          f"{int(t[s, :, native.SVT_ARRIVED].sum()):>12}")
         return "\n".join(lines)
