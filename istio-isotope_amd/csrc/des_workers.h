@@ -1,6 +1,7 @@
 // DES worker pools: W workers per replica behind one
 // FIFO queue, on the item engine.  A part of des_items.hip, included inside
-// namespace isim::dit after k_qscan (it uses kT, gid, nthreads and MP).
+// namespace isim::dit where des_items_queue.h ends (it uses kT, gid, nthreads
+// and MP).
 //
 // With a constant hold h the request of FIFO rank p of a replica starts at
 //   S_p = max(a_p, S_{p-W} + h),
@@ -8,7 +9,7 @@
 // sub-queue p mod W, where it is request p div W.  k_qscan and the scan by key
 // solve a one-worker queue over any contiguous run in FIFO order with one
 // hold, so all a pooled round needs is its order REFINED: every (row, replica)
-// segment of the round's FIFO order (k_pairs0 / k_pairs1 / k_pairs2's arrays)
+// segment of the round's FIFO order (k_pairs<SRC>'s or k_pairs2's arrays)
 // laid out as its min(W, L) rank classes, each contiguous and in FIFO order,
 // each a segment of its own.
 //

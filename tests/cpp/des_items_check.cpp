@@ -174,9 +174,10 @@ int main(int argc, char **argv) {
   }
   // the engine's own choices, restated: the first quiet pass of a cyclic
   // schedule starts its cut step begins from the contention-free callee
-  // maxima (des_items.hip k_relmax), and a round the plan marks sort-free
-  // (DesPlan::round_nosort) takes its items in (position, item) order, a
-  // zero-hold item starting at its own arrival (k_pairs0)
+  // maxima (des_items_prewalk.h k_relmax), and a round the plan marks
+  // sort-free (DesPlan::round_nosort) takes its items in (position, item)
+  // order, a zero-hold item starting at its own arrival (des_items_queue.h
+  // qalone)
   dur_of.resize(M, 0);
   std::vector<uint64_t> relmax(M * aw, 0);
   for (uint64_t i = 0; i < M; ++i) {

@@ -225,6 +225,35 @@ def test_items_two_sort_queue_path(gpu, name):
     DesCase(CASES[name](), 500_000, flags=native.FLAG_DES_TWO_SORTS).compare(31, 2500)
 
 
+# case: (traces, mean gap ns) — the sizes and gaps of the neighbouring tests
+ORDER_SOURCES = {"zero_hold_mix": (2500, 500_000), "tree_reps_p70": (2500, 500_000), "mesh_des": (1500, 400_000)}
+SCANS = {"qscan": 0, "by_key": native.FLAG_DES_SCAN_BY_KEY,
+         "two_sorts_by_key": native.FLAG_DES_TWO_SORTS | native.FLAG_DES_SCAN_BY_KEY}
+
+
+@pytest.mark.parametrize("scan", list(SCANS))
+@pytest.mark.parametrize("name", sorted(ORDER_SOURCES))
+def test_items_order_sources_through_both_scans(gpu, name, scan):
+    """Every source of a round's queue order through both
+    scans, against the event oracle: the list of a sort-free round with
+    zero-hold items among it (zero_hold_mix: kQList), one sort's keys
+    (tree_reps_p70: kQSorted) and a cyclic schedule's kept orders (mesh_des:
+    kQKept, next to the sorts its first passes do).  k_qscan reads each at its
+    source; under ISIM_FLAG_DES_SCAN_BY_KEY the one k_pairs<SRC> writes it out
+    for rocPRIM's scan by key and k_qout, and with ISIM_FLAG_DES_TWO_SORTS the
+    two-sort path writes the arrays itself.  Every trace executes the entry, so
+    the entry's round holds n items: 2,500 (four 512-item k_qscan tiles and
+    452) or 1,500 (two and 476), more than 1,024 with a ragged tail, so
+    segments cross tile boundaries and the look-back runs; over all rounds the
+    oracle counts 17,009, 29,156 and 14,870 executed invocations at these
+    sizes (z of zero_hold_mix alone: 7,500 in its rounds)."""
+    n, mean = ORDER_SOURCES[name]
+    c = DesCase(CASES[name](), mean, flags=SCANS[scan])
+    assert c.d.info.items == 1 and c.d.info.cyclic == (name != "tree_reps_p70")
+    recs, _, _ = c.compare(31, n)
+    assert c.d.last_batch()["items"] == int(recs["hops"].sum()) > 1024 + n
+
+
 def test_items_c5p_bench_batch_sparse_load(gpu):
     """c5p exactly as bench.py builds it, at its bench batch (2^19 traces),
     under a sparse load (mean gap 17 s against ~35 ms latencies): the
@@ -258,7 +287,8 @@ def test_items_c5p_bench_batch_sparse_load(gpu):
 @pytest.mark.parametrize("mean", [50_000, 400_000])
 def test_items_kept_queue_order(gpu, mean):
     """A cyclic schedule's quiet passes reuse a sort round's previous sorted
-    order when it still sorts the new arrivals (k_ordchk / k_pairs1o); under
+    order when it still sorts the new arrivals (k_ordchk; the kQKept source
+    of k_qscan and k_pairs); under
     heavy and light contention, at a size where some kept orders hold and
     some fail, everything equals the run that sorts every round
     (ISIM_FLAG_DES_SORT_ALL) and, at a smaller size, the oracle."""

@@ -46,6 +46,17 @@ def _mixed():
         {"name": "z"}]}
 
 
+def _zero_hold():
+    """b and the sleep-free z arrive in one round, a's call step, both in trace order behind a's one replica:
+    a sort-free round (its list is its FIFO order) in which z's items are each a segment of their own next to
+    b's one segment.  (The item suite's zero_hold_mix has a cyclic schedule, which takes no pools.)"""
+    return {"services": [
+        {"name": "a", "isEntrypoint": True,
+         "script": [{"sleep": "200us"}, [{"call": {"service": "b", "probability": 50}}, {"call": "z"}]]},
+        {"name": "b", "script": [{"sleep": "700us"}]},
+        {"name": "z"}]}
+
+
 def _ties_paced():
     """Zero hop cost and a paced load of one request per 200 us: b's arrivals through c of trace t - 1 and
     straight from a of trace t meet at the same instant, so (trace, hop) decides their ranks."""
@@ -78,6 +89,7 @@ GRAPHS = {
             300_000, 2000, 2),
     "ties_paced": (_ties_paced, isim.MODE_A, dict(flags=DYN, **NOHOP), 200_000, 2000, {"b": 3}),
     "ties_fanout": (_ties_fanout, isim.MODE_A, {}, 1, 1500, {"a": 2, "z": 3}),
+    "zero_hold": (_zero_hold, isim.MODE_A, {}, 150_000, 2500, {"b": 3}),
 }
 BEGIN = 1000
 

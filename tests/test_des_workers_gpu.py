@@ -116,6 +116,25 @@ def test_a_round_of_pooled_and_single_rows(gpu):
     assert not np.any(w & (s["service"] == names.index("z")))   # no hold: nobody ever waits for z
 
 
+def test_a_sort_free_round_with_zero_holds_by_key(gpu):
+    """b (3 workers) and the zero-hold z in one sort-free round under ISIM_FLAG_DES_SCAN_BY_KEY: the list written
+    out by k_pairs<kQList>, z's items under keys that differ from both neighbours', read by wk_head and then by
+    rocPRIM's scan by key; k_qscan over the same refined arrays agrees.  (zero_hold_mix itself cannot carry a
+    pool: its schedule is cyclic, which isim_des_workers_set refuses.)"""
+    workers = GRAPHS["zero_hold"][5]
+    c, r, s = check("zero_hold", workers, SBK)
+    names = [x["name"] for x in c.h.graph.canonical()["services"]]
+    w = s["start_ns"] > s["arrival_ns"]
+    assert np.any(w & (s["service"] == names.index("b"))) and not np.any(w & (s["service"] == names.index("z")))
+    # every round is sort-free: the item count, the buckets and the fault word are all the host reads back
+    c.d.serve(BEGIN, GRAPHS["zero_hold"][4])
+    assert c.d.last_batch()["syncs"] == 3
+    _, r0, s0 = device("zero_hold", workers, 0)
+    assert np.array_equal(s0, s)
+    for f in ("recs", "stats", "table", "wait"):
+        assert np.array_equal(r0[f], r[f]), f
+
+
 SOURCES = [("prob", BEGIN, None), ("modeb", BEGIN, None), ("wide", BEGIN, None), ("t64", BEGIN, None),
            ("prob", (1 << 32) - 300, 601), ("mixed", (1 << 32) - 300, 601)]
 
