@@ -133,7 +133,7 @@ typedef struct {
 #define ISIM_ST_MAX_LATENCY 6
 #define ISIM_ST_DES_RETRY 7       /* DES batches NOT accumulated: low 32 bits, a latency reached 2^31 ns in
                                      32-bit rows (rerun them with ISIM_DES_FLAG_WIDE; isim_serve_des does), or
-                                     a cyclic schedule found no fixed point within 256 passes; high 32 bits,
+                                     a cyclic schedule found no fixed point within 4096 passes; high 32 bits,
                                      batches FAILED by a device fault (a queue pass's decoupled look-back gave
                                      up waiting for an earlier tile: an error, never retried — isim_serve_des
                                      and the item engine return ISIM_EHIP; such a batch writes no record and

@@ -749,11 +749,14 @@ int des_launch(const DesLaunch &L, void *stream_) {
     for (; p < kMaxPasses; ++p) {
       if (hipMemsetAsync(kq.changed, 0, 4, stream) != hipSuccess) return 1;
       if (pass(kq)) return 1;
-      uint32_t changed = 1;
-      if (hipMemcpyAsync(&changed, kq.changed, 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      // the overflow word and, behind it, the changed flag (des_layout.h): a batch
+      // that is dropped anyway (a 32-bit row value reached 2^31, a look-back
+      // fault) has no fixed point to wait for — its rows may never settle
+      uint32_t flags[2] = {0, 1};
+      if (hipMemcpyAsync(flags, B.ovf, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
           hipStreamSynchronize(stream) != hipSuccess)
         return 1;
-      if (!changed) break;
+      if (flags[0] || !flags[1]) break;
     }
     if (p == kMaxPasses) {
       static const uint32_t no_fixed_point = 2;

@@ -268,7 +268,7 @@ int serve_des_host(isim_handler *h, int device, uint32_t flags0, uint64_t n_trac
                                   "(device fault flag); the batch was not accumulated");
     if ((flags & ISIM_DES_FLAG_WIDE) || h->des.items)
       return set_error(ISIM_EINVAL, "DES batch not accumulated with 64-bit rows: the cyclic schedule found no fixed "
-                                    "point within 256 passes (or arrivals beyond the sort keys)");
+                                    "point within 4096 passes (or arrivals beyond the sort keys)");
     flags |= ISIM_DES_FLAG_WIDE;
   }
   if (h_stats)

@@ -306,6 +306,50 @@ def test_items_kept_queue_order(gpu, mean):
     assert np.array_equal(np.asarray(got[2]), np.asarray(ref[2]))
 
 
+def _overloaded_cycle():
+    """The seeded random family's dynamic-6 (tests/random_des_graphs.py), written out: s6 and s7 (one and
+    five replicas, 7 and 14 ms) are reached in s0's first call step and again, through s1 .. s5, in its
+    second, so their queues depend on their own finishes; at a 60 us gap latencies reach 67 s."""
+    def call(s, p=None, size=None):
+        c = {"service": s}
+        if size is not None:
+            c["size"] = size
+        if p is not None:
+            c["probability"] = p
+        return {"call": c}
+
+    def svc(name, script, err, resp, reps):
+        return {"name": name, "script": script, "errorRate": err, "responseSize": resp, "numReplicas": reps}
+
+    doc = {"defaults": {"requestSize": 100}, "services": [
+        svc("s0", [{"sleep": "16ms"}, call("s6", 100, 4791), call("s1", 100, 4403)], 0.001, 33667, 1),
+        svc("s1", [call("s2", 99, 4470), {"sleep": "24ms"}, call("s2", 1)], 1.0, 95371, 1),
+        svc("s2", [call("s3", 99), call("s3", 50), call("s7", 100), []], 0.5, 5491, 70),
+        svc("s3", [call("s4", 100, 4474)], 1.0, 92579, 3),
+        svc("s4", [[], {"sleep": "18ms"}, [call("s5", 50, 943), call("s5", 0, 264)], call("s5", None, 2733)],
+            1.0, 55769, 3),
+        svc("s5", [[call("s7", 99), {"sleep": "1ms"}], [call("s6", 99, 879), {"sleep": "8ms"}, {"sleep": "-1ms"}],
+                   call("s6"), call("s7", 30)], 0.5, 12402, 5),
+        svc("s6", [call("s7", 0), call("s7", 30), [{"sleep": "2ms"}, call("s7", 30), {"sleep": "5ms"}]],
+            0, 95464, 1),
+        svc("s7", [[{"sleep": "-1ms"}, {"sleep": "9ms"}, {"sleep": "5ms"}]], 0, 35270, 5)]}
+    doc["services"][0]["isEntrypoint"] = True
+    return doc
+
+
+def test_items_overloaded_cycle_past_256_passes(gpu):
+    """A cyclic schedule under overload: the backlog spans many lookahead windows and the fixed point takes
+    hundreds of passes (356 here; 156 on the first 293 traces).  Both engines dropped a batch at 256 passes
+    (EINVAL from isim_serve_des) though the iteration converges — found by tests/test_random_des_gpu.py on
+    this graph; kMaxPasses (csrc/des.h) is 4096 now."""
+    c = DesCase(_overloaded_cycle(), 60_000, seed=6470602850060597898, hop_base_ns=1, req_ps_per_byte=80,
+                resp_ps_per_byte=10 ** 6)
+    assert c.d.info.items == 1 and c.d.info.cyclic == 1
+    recs, _, _ = c.compare(6_000_018, 1100)
+    assert int(recs["latency_ns"].max()) > 60_000_000_000
+    assert 256 < c.d.last_batch()["passes"] < 1024
+
+
 def _bench_case(cfg, flags=0):
     import bench
     j, _ = bench.build_graph(cfg)
