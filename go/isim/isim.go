@@ -550,6 +550,58 @@ func (h *Handler) ServiceTimelineMerge(dst, src []uint64, t0Ns, windowNs uint64,
 	return lastErr(C.isim_service_timeline_merge(h.h, &p, u64ptr(dst), u64ptr(src)))
 }
 
+// Per-service percentiles (DESIGN §28): per service, measure (SvqWait,
+// SvqService, SvqDuration) and class a cell of 1 + len(qPpm) words (the count,
+// then the order statistics), then SvqHeaderWords words (SvqHFolded, SvqHRefused).
+const (
+	SvqWait        = C.ISIM_SVQ_WAIT
+	SvqService     = C.ISIM_SVQ_SERVICE
+	SvqDuration    = C.ISIM_SVQ_DURATION
+	SvqMeasures    = C.ISIM_SVQ_MEASURES
+	SvqClasses     = C.ISIM_SVQ_CLASSES
+	SvqHFolded     = C.ISIM_SVQ_H_FOLDED
+	SvqHRefused    = C.ISIM_SVQ_H_REFUSED
+	SvqHeaderWords = C.ISIM_SVQ_HEADER_WORDS
+)
+
+// ServiceQuantiles selects, on GPU `device`, the exact percentiles qPpm of the
+// queue wait, service time and duration of every service over spans (every span
+// of a whole tapped batch, in any order) into a new table (isim_service_quantiles).
+func (h *Handler) ServiceQuantiles(device int, spans []DesSpan, qPpm []uint32) ([]uint64, error) {
+	var words C.uint64_t
+	if err := lastErr(C.isim_service_quantiles_table_words(h.h, C.uint32_t(len(qPpm)), &words)); err != nil {
+		return nil, err
+	}
+	table := make([]uint64, words)
+	var sp *C.isim_des_span
+	if len(spans) > 0 {
+		sp = (*C.isim_des_span)(unsafe.Pointer(&spans[0]))
+	}
+	q := u32ptr(qPpm)
+	if err := lastErr(C.isim_service_quantiles(C.int(device), h.h, q, C.uint32_t(len(qPpm)), sp, C.uint64_t(len(spans)), u64ptr(table))); err != nil {
+		return nil, err
+	}
+	return table, nil
+}
+
+// ServiceQuantilesHost is ServiceQuantiles on the CPU (isim_service_quantiles_host).
+func (h *Handler) ServiceQuantilesHost(spans []DesSpan, qPpm []uint32) ([]uint64, error) {
+	var words C.uint64_t
+	if err := lastErr(C.isim_service_quantiles_table_words(h.h, C.uint32_t(len(qPpm)), &words)); err != nil {
+		return nil, err
+	}
+	table := make([]uint64, words)
+	var sp *C.isim_des_span
+	if len(spans) > 0 {
+		sp = (*C.isim_des_span)(unsafe.Pointer(&spans[0]))
+	}
+	q := u32ptr(qPpm)
+	if err := lastErr(C.isim_service_quantiles_host(h.h, q, C.uint32_t(len(qPpm)), sp, C.uint64_t(len(spans)), u64ptr(table))); err != nil {
+		return nil, err
+	}
+	return table, nil
+}
+
 // SelectTraces returns the ids begin + i of the records with a latency of at
 // least minLatencyNs in class cls (C.ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500), in
 // ascending i, at most maxIDs of them, and the number of matching records
@@ -662,6 +714,13 @@ type Multi struct{ m *C.isim_multi }
 
 // u64ptr passes an empty slice as NULL (libisim then reports EINVAL) instead
 // of panicking on &s[0].
+func u32ptr(s []uint32) *C.uint32_t {
+	if len(s) == 0 {
+		return nil
+	}
+	return (*C.uint32_t)(unsafe.Pointer(&s[0]))
+}
+
 func u64ptr(s []uint64) *C.uint64_t {
 	if len(s) == 0 {
 		return nil

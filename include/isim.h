@@ -1289,6 +1289,76 @@ ISIM_API int isim_service_timeline_host(const isim_handler *h, const isim_timeli
 ISIM_API int isim_service_timeline(int device, const isim_handler *h, const isim_timeline_params *p,
                                    const isim_des_span *h_spans, uint64_t n_spans, uint64_t *h_table);
 
+/* ---- per-service exact percentiles of queue wait, service time and duration (EXT) ----
+ * The per-service view of service_request_duration_seconds: for every service
+ * the exact order statistics of three measures over the isim_des_span records
+ * of a tapped batch (threshold 0: every executed invocation).
+ *
+ * A span is refused by the rule of isim_service_timeline: service >=
+ * n_services, or a <= S <= F does not hold (a = arrival_ns, S = start_ns,
+ * F = finish_ns).  A refused span counts in ISIM_SVQ_H_REFUSED and in nothing
+ * else; the host and the device refuse the same spans.
+ *
+ * Measures, per span that is not refused: */
+#define ISIM_SVQ_WAIT     0   /* S - a: the queue wait */
+#define ISIM_SVQ_SERVICE  1   /* F - S: from the worker taking it to the respond point */
+#define ISIM_SVQ_DURATION 2   /* F - a: what RecordResponseSent observes */
+#define ISIM_SVQ_MEASURES 3
+/* Classes: ISIM_Q_ALL, ISIM_Q_200, ISIM_Q_500, the code being status bit 0. */
+#define ISIM_SVQ_CLASSES  3
+/* The table: u64 [n_services][ISIM_SVQ_MEASURES][ISIM_SVQ_CLASSES][1 + n_q],
+ * then a header of ISIM_SVQ_HEADER_WORDS words.  Word 0 of a cell is the count
+ * N of that service and class (the same for the three measures); word 1 + i is
+ * the k-th smallest value of the measure among them, k =
+ * isim_quantile_rank(N, q_ppm[i]); every word of a cell is 0 where N is 0.
+ * The table is WRITTEN, not added into (order statistics do not merge): every
+ * word is written by the call, and the table may be dirty.  q_ppm: the rules of
+ * isim_latency_quantiles (1 .. ISIM_MAX_QUANTILES entries, each <= 1,000,000,
+ * copied at the call). */
+#define ISIM_SVQ_H_FOLDED  0   /* spans folded */
+#define ISIM_SVQ_H_REFUSED 1   /* spans refused */
+#define ISIM_SVQ_HEADER_WORDS 2
+#define ISIM_SVQ_MAX_SPANS 0xFFFFFFFFull   /* u32 counters, offsets and ranks */
+/* The device call selects a service with at most ISIM_SVQ_STAGE spans in LDS,
+ * one workgroup per service.  A longer segment is cut into chunks of
+ * ISIM_SVQ_CHUNK elements that many workgroups histogram, digit by digit. */
+#define ISIM_SVQ_STAGE 3584
+#define ISIM_SVQ_CHUNK 4096
+#define ISIM_SVQ_SLOT_BYTES 3584   /* workspace of a long segment besides its bins */
+
+/* Every call below returns ISIM_EINVAL, before any HIP call, for a handler
+ * isim_serve_des_spans_device refuses with a tap, a null argument, a quantile
+ * list isim_latency_quantiles refuses, or more than ISIM_SVQ_MAX_SPANS spans. */
+/* host only, no GPU: n_services * 9 * (1 + n_q) + ISIM_SVQ_HEADER_WORDS */
+ISIM_API int isim_service_quantiles_table_words(const isim_handler *h, uint32_t n_q, uint64_t *words);
+/* host only, no GPU.  With P(x) = x rounded up to a multiple of 256:
+ *   256 + 3 * P(8 * n_services)                        per service: counts, offsets and cursors by (service, code)
+ *   + 24 * cap_spans                                   per span: its three measures, scattered by service
+ *   + L * (ISIM_SVQ_SLOT_BYTES + 9 * n_q * 1024)       per long segment: select states and u32 bins
+ * where L = min(n_services, cap_spans / (ISIM_SVQ_STAGE + 1)) is the most long segments cap_spans spans can form. */
+ISIM_API int isim_service_quantiles_workspace_bytes(const isim_handler *h, uint64_t cap_spans, uint32_t n_q,
+                                                    uint64_t *bytes);
+/* The table of the spans that a preceding isim_serve_des_spans_device wrote to
+ * d_spans, on the current device, asynchronously on hip_stream.  The span
+ * count is read on the device: d_off[d_info[ISIM_SPAN_WRITTEN]], bounded by
+ * cap_spans (which sizes the grids and the workspace); d_off and d_info are the
+ * tap's.  WRITES d_out.  A fixed sequence of kernels that does not depend on
+ * the data: no host synchronisation, no allocation, graph-capturable from the
+ * first call, the workspace may be dirty (calls that share one must be
+ * ordered).  cap_spans 0 writes zeros and needs no workspace.  Also
+ * ISIM_EINVAL: buffers not 8-byte aligned (d_spans 16), a workspace below
+ * isim_service_quantiles_workspace_bytes. */
+ISIM_API int isim_service_quantiles_device(const isim_handler *h, const uint32_t *q_ppm, uint32_t n_q,
+                                           const uint64_t *d_off, const isim_des_span *d_spans, uint64_t cap_spans,
+                                           const uint64_t *d_info, uint64_t *d_out, void *d_workspace,
+                                           uint64_t workspace_bytes, void *hip_stream);
+/* host only, no GPU: the same table on the CPU over h_spans[0 .. n_spans) (a sort per service, measure and class) */
+ISIM_API int isim_service_quantiles_host(const isim_handler *h, const uint32_t *q_ppm, uint32_t n_q,
+                                         const isim_des_span *h_spans, uint64_t n_spans, uint64_t *h_out);
+/* Synchronous convenience: host buffers, on GPU `device`. */
+ISIM_API int isim_service_quantiles(int device, const isim_handler *h, const uint32_t *q_ppm, uint32_t n_q,
+                                    const isim_des_span *h_spans, uint64_t n_spans, uint64_t *h_out);
+
 #ifdef __cplusplus
 }
 #endif

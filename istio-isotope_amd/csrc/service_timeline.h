@@ -82,12 +82,17 @@ struct Upd {
   uint64_t wait = 0;
   Interval q, b;  // [a, S) and [S, S + P_s)
 };
-// hold: P_s per service.  A refused span (service out of range, or not a <= S <= F) yields the empty Upd.
+// the span rule (also service_quantiles.h's): refused if the service is out of range or a <= S <= F does not hold
+ISIM_TL_FN bool span_refused(uint32_t n_services, uint64_t arrival, uint64_t start, uint64_t finish, uint32_t service) {
+  return service >= n_services || arrival > start || start > finish;
+}
+
+// hold: P_s per service.  A refused span (span_refused) yields the empty Upd.
 template <typename A>
 ISIM_TL_FN Upd span_updates(const A &a, uint32_t n_services, const uint64_t *hold, uint64_t arrival, uint64_t start,
                             uint64_t finish, uint32_t service, uint32_t status) {
   Upd u;
-  if (service >= n_services || arrival > start || start > finish) return u;
+  if (span_refused(n_services, arrival, start, finish, service)) return u;
   const uint32_t base = service * (a.n_windows + 2u);
   u.ka = base + tl::row_of(a, arrival);
   u.ks = base + tl::row_of(a, start);

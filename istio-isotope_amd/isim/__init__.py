@@ -31,3 +31,6 @@ from .spans import (SPAN_DTYPE, CriticalPath, Trace, TraceSpans, select_traces, 
 from .service_timeline import (ServiceTimeline, service_holds, service_timeline, service_timeline_device,  # noqa: F401
                                service_timeline_host, service_timeline_table_words,
                                service_timeline_workspace_bytes)
+from .service_quantiles import (MEASURE_NAMES, ServiceQuantiles, decode_service_quantiles,  # noqa: F401
+                                service_quantiles, service_quantiles_device, service_quantiles_host,
+                                service_quantiles_table_words, service_quantiles_workspace_bytes)

@@ -92,6 +92,16 @@ DCP_H_TRACES, DCP_H_SPANS, DCP_H_CRITICAL, DCP_H_SUM_LATENCY, DCP_H_REFUSED = ra
 SVT_ARRIVED, SVT_STARTED, SVT_FINISHED, SVT_SUM_WAIT, SVT_MAX_WAIT, SVT_QUEUED_NS, SVT_BUSY_NS = 0, 1, 2, 4, 5, 6, 7
 SVT_ROW_WORDS = 8
 SVT_H_FOLDED, SVT_H_REFUSED = 0, 1
+# isim_service_quantiles*: measures, header words and the device call's segment sizes (isim.h ISIM_SVQ_*)
+SVQ_WAIT, SVQ_SERVICE, SVQ_DURATION = range(3)
+SVQ_MEASURES = 3
+SVQ_CLASSES = 3
+SVQ_H_FOLDED, SVQ_H_REFUSED = 0, 1
+SVQ_HEADER_WORDS = 2
+SVQ_MAX_SPANS = 0xFFFFFFFF
+SVQ_STAGE = 3584
+SVQ_CHUNK = 4096
+SVQ_SLOT_BYTES = 3584
 SVT_MAX_CELLS = 1 << 24
 
 
@@ -326,6 +336,12 @@ SIGNATURES = {
                                                C.c_uint64, _VP]),
     "isim_service_timeline_host": (C.c_int, [_VP, C.POINTER(TimelineParams), _VP, C.c_uint64, _VP]),
     "isim_service_timeline": (C.c_int, [C.c_int, _VP, C.POINTER(TimelineParams), _VP, C.c_uint64, _VP]),
+    "isim_service_quantiles_table_words": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "isim_service_quantiles_workspace_bytes": (C.c_int, [_VP, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "isim_service_quantiles_device": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, C.c_uint64, _VP, _VP, _VP,
+                                                C.c_uint64, _VP]),
+    "isim_service_quantiles_host": (C.c_int, [_VP, _VP, C.c_uint32, _VP, C.c_uint64, _VP]),
+    "isim_service_quantiles": (C.c_int, [C.c_int, _VP, _VP, C.c_uint32, _VP, C.c_uint64, _VP]),
 }
 
 _lib = None
