@@ -12,7 +12,7 @@
 #include "../../include/isim.h"
 #include "host_stage.h"
 #include "quantile_rank.h"
-#include "radix_select.h"
+#include "segmented_select.h"
 #include "trace_rec_dev.h"
 
 namespace {
@@ -23,10 +23,10 @@ using rs::kBins;
 using rs::kClasses;
 using rs::kMaxQ;
 
-constexpr uint32_t kHistThreads = 512;  // 3 workgroups of 48 KB LDS per CU: 24 waves
+using rs::kHistThreads;
+using rs::kResolveThreads;
+using rs::kUnroll;
 constexpr uint32_t kHistMaxGrid = 768;  // 3 per CU; a workgroup's u32 LDS bins hold 2^40 / 768 < 2^32 records
-constexpr uint32_t kUnroll = 4;         // records per lane in flight
-constexpr uint32_t kResolveThreads = 64 * kMaxQ;
 constexpr uint64_t kMaxRecords = 1ull << 40;
 
 int qfail(const std::string &msg) { return isim::set_error(ISIM_EINVAL, msg); }
@@ -40,10 +40,6 @@ struct QState {
   rs::State<uint64_t> sel;
 };
 
-struct QArgs {
-  uint32_t ppm[kMaxQ];
-};
-
 constexpr uint64_t kStateBytes = (sizeof(QState) + 255) & ~255ull;
 static_assert(kStateBytes == 1536, "isim_quantiles_workspace_bytes is pinned");
 
@@ -55,7 +51,7 @@ using isim::q::nearest_rank;  // quantile_rank.h
 // or the output of an empty batch.  A kernel like the rest of the sequence, so
 // a captured call is a chain of kernel nodes only.
 __global__ __launch_bounds__(1024) void k_quantile_clear(unsigned long long *words, uint32_t n_words) {
-  for (uint32_t i = threadIdx.x; i < n_words; i += 1024) words[i] = 0;
+  rs::clear_words<1024>(words, n_words);
 }
 
 // Pass 0: per class the record count, and the OR of the latencies.
@@ -89,97 +85,43 @@ __global__ __launch_bounds__(256) void k_quantile_count(const rec4 *__restrict__
 
 // After pass 0: the ranks from the counts (on the device: the host never sees
 // the class counts), one group per non-empty class, the first digit pass.
-__global__ __launch_bounds__(64) void k_quantile_setup(QState *st, uint64_t n, QArgs q, uint32_t n_q, uint64_t *out) {
+__global__ __launch_bounds__(64) void k_quantile_setup(QState *st, uint64_t n, rs::Ppm q, uint32_t n_q, uint64_t *out) {
   const uint32_t t = threadIdx.x;
   const uint64_t n500 = st->cnt[ISIM_Q_500];
   const uint64_t any = st->any;
   __syncthreads();  // every thread has read cnt[500] before thread 0 rewrites the counts
-  const uint64_t cnt[kClasses] = {n, n - n500, n500};
-  if (t < kClasses * kMaxQ) {
-    const uint32_t c = t / kMaxQ, i = t % kMaxQ;
-    rs::init(st->sel, c, i, n_q, cnt[c], q.ppm);
-    if (i == 0) {
-      st->cnt[c] = cnt[c];
-      out[c * (1 + n_q)] = cnt[c];
-    }
+  rs::setup(st->sel, t, n_q, n, n - n500, n500, q, (unsigned long long *)out);
+  if (t == 0) {
+    st->cnt[ISIM_Q_ALL] = n;
+    st->cnt[ISIM_Q_200] = n - n500;
+    st->top_byte = rs::top_byte(any);
   }
-  if (t == 0) st->top_byte = rs::top_byte(any);
 }
 
-// Digit pass `byte`: per (class, group) a 256-bin histogram of that byte over
-// the records whose higher bytes equal the group's prefix, in LDS; one flush
-// per workgroup into the global u64 histogram.
+// Digit pass `byte`: rs::hist_pass over a grid-stride share of the records,
+// into the global u64 histogram.
 __global__ __launch_bounds__(kHistThreads) void k_quantile_hist(const rec4 *__restrict__ rec, uint64_t n,
                                                                const QState *__restrict__ st,
                                                                unsigned long long *__restrict__ ghist, uint32_t n_q,
                                                                int byte) {
-  __shared__ uint32_t hist[kClasses * kMaxQ * kBins];
-  __shared__ uint64_t s_prefix[kClasses][kMaxQ];
-  __shared__ uint32_t s_ngrp[kClasses];
+  __shared__ rs::HistLds lds;
   if (byte > st->top_byte) return;  // every latency is zero in this byte: the prefixes keep a zero digit
-  const uint32_t t = threadIdx.x;
-  if (t < kClasses) s_ngrp[t] = min(st->sel.ngrp[t], n_q);
-  if (t < kClasses * kMaxQ) s_prefix[t / kMaxQ][t % kMaxQ] = st->sel.gprefix[t / kMaxQ][t % kMaxQ];
-  __syncthreads();
-  uint32_t ngrp[kClasses];
-  for (uint32_t c = 0; c < kClasses; ++c) {
-    ngrp[c] = s_ngrp[c];
-    for (uint32_t i = t; i < ngrp[c] * kBins; i += kHistThreads) hist[c * kMaxQ * kBins + i] = 0;
-  }
-  __syncthreads();
-
-  const uint32_t lane = t & 63u;
-  const uint64_t wave = (uint64_t)blockIdx.x * (kHistThreads / 64) + (t >> 6);
+  // a wave takes 64 * kUnroll consecutive records per step
+  const uint64_t wave = (uint64_t)blockIdx.x * (kHistThreads / 64) + (threadIdx.x >> 6);
   const uint64_t step = (uint64_t)gridDim.x * (kHistThreads / 64) * (64 * kUnroll);
-  // a wave takes 64 * kUnroll consecutive records per step; the loop bound is wave-uniform
-  for (uint64_t base = wave * (64 * kUnroll); base < n; base += step) {
-    rec4 r[kUnroll];
-#pragma unroll
-    for (uint32_t u = 0; u < kUnroll; ++u) {
-      const uint64_t i = base + u * 64 + lane;
-      r[u] = isim::dev::load_rec(rec, i, i < n);
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < kUnroll; ++u)
-      rs::count_key(hist, isim::dev::latency(r[u]), base + u * 64 + lane < n, byte, 1u + isim::dev::code(r[u]), s_prefix,
-                    ngrp[ISIM_Q_ALL], ngrp[ISIM_Q_200], ngrp[ISIM_Q_500], lane);
-  }
-  __syncthreads();
-  for (uint32_t c = 0; c < kClasses; ++c)
-    for (uint32_t i = t; i < ngrp[c] * kBins; i += kHistThreads) {
-      const uint32_t v = hist[c * kMaxQ * kBins + i];
-      if (v) atomicAdd(&ghist[(uint64_t)c * n_q * kBins + i], (unsigned long long)v);
-    }
+  const auto keys = [&] {
+    return [=](uint64_t i, bool live) {
+      const rec4 r = isim::dev::load_rec(rec, i, live);
+      return rs::Key{isim::dev::latency(r), 1u + isim::dev::code(r)};
+    };
+  };
+  rs::hist_pass(lds, st->sel, n_q, byte, wave * (64 * kUnroll), n, step, keys, ghist);
 }
 
-// After digit pass `byte`: the resolve per (class, quantile), then the regroup
-// (radix_select.h), and the histogram is cleared.  One workgroup, wave i takes
-// quantile i of every class.  After byte 0 the prefixes are the values.
+// After digit pass `byte`, one workgroup: rs::resolve_pass.
 __global__ __launch_bounds__(kResolveThreads) void k_quantile_resolve(QState *st, unsigned long long *ghist,
                                                                      uint32_t n_q, int byte, uint64_t *out) {
-  const uint32_t t = threadIdx.x, lane = t & 63u, i = t >> 6;
-  if (byte <= st->top_byte) {
-    if (i < n_q) {
-      for (uint32_t c = 0; c < kClasses; ++c) {
-        const uint64_t k = st->sel.k[c][i];
-        if (!k) continue;  // empty class
-        const uint32_t g = min(st->sel.grp[c][i], n_q - 1);
-        const unsigned long long *h = ghist + ((uint64_t)c * n_q + g) * kBins + lane * 4;
-        uint32_t digit;
-        uint64_t below;
-        if (rs::resolve<uint64_t>(h[0], h[1], h[2], h[3], k, lane, digit, below))
-          rs::take_digit(st->sel, c, i, digit, k, below);
-      }
-    }
-    __syncthreads();  // every wave has read its bins and written its prefix
-    if (t < kClasses) rs::regroup(st->sel, t, n_q);
-    for (uint32_t w = t; w < kClasses * n_q * kBins; w += kResolveThreads) ghist[w] = 0;
-  }
-  if (byte == 0) {
-    __syncthreads();
-    if (t < kClasses * kMaxQ && t % kMaxQ < n_q)
-      out[(t / kMaxQ) * (1 + n_q) + 1 + t % kMaxQ] = st->sel.k[t / kMaxQ][t % kMaxQ] ? st->sel.prefix[t / kMaxQ][t % kMaxQ] : 0;
-  }
+  rs::resolve_pass(st->sel, ghist, n_q, byte, st->top_byte, (unsigned long long *)out);
 }
 
 int check_q(const uint32_t *q_ppm, uint32_t n_q, uint64_t n_records) {
@@ -228,13 +170,11 @@ int isim_latency_quantiles_device(const isim_trace_rec *d_records, uint64_t n_re
   QState *st = (QState *)d_workspace;
   unsigned long long *ghist = (unsigned long long *)((char *)d_workspace + kStateBytes);
   const rec4 *rec = (const rec4 *)d_records;
-  QArgs q{};
-  for (uint32_t i = 0; i < n_q; ++i) q.ppm[i] = q_ppm[i];
   hipLaunchKernelGGL(k_quantile_clear, dim3(1), dim3(1024), 0, s, (unsigned long long *)d_workspace,
                      (uint32_t)(workspace_bytes(n_q) / 8));
   const uint32_t count_grid = (uint32_t)std::min<uint64_t>((n_records + 1023) / 1024, 2048);
   hipLaunchKernelGGL(k_quantile_count, dim3(count_grid), dim3(256), 0, s, rec, n_records, st);
-  hipLaunchKernelGGL(k_quantile_setup, dim3(1), dim3(64), 0, s, st, n_records, q, n_q, d_out);
+  hipLaunchKernelGGL(k_quantile_setup, dim3(1), dim3(64), 0, s, st, n_records, rs::ppm_of(q_ppm, n_q), n_q, d_out);
   const uint64_t per_wg = kHistThreads * kUnroll;
   const uint32_t hist_grid = (uint32_t)std::min<uint64_t>((n_records + per_wg - 1) / per_wg, kHistMaxGrid);
   for (int byte = 7; byte >= 0; --byte) {

@@ -2,10 +2,12 @@
 // most significant byte down, per (class, group) a 256-bin histogram of the
 // byte over the keys whose higher bytes equal the group's prefix, then per
 // (class, quantile) the digit at which the running count reaches its rank.
-// quantile.hip runs the steps as launches over a whole batch (u64 counts in
-// global memory), timeline_quantiles.hip as a loop over one row (u32 counts in
-// LDS).  A group is one still-distinct prefix of a class: quantiles that share
-// a prefix share a histogram.
+// The loops that run the steps are segmented_select.h's: as launches with the
+// counts in global memory (quantile.hip's batch, u64; service_quantiles.hip's
+// long segments, u32) or as a loop of one workgroup with u32 counts in LDS
+// (a row of timeline_quantiles.hip, a short segment of service_quantiles.hip).
+// A group is one still-distinct prefix of a class: quantiles that share a
+// prefix share a histogram.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -10,14 +10,14 @@
 //                  with the first of its chunks of kChunk elements
 //   k_svq_scatter  the three measures of a span to its segment, three arrays
 //   k_svq_short    a workgroup claims a service by ticket; a short segment is
-//                  staged in LDS and selected there, once per measure (§15's
-//                  loop over radix_select.h's steps)
+//                  staged in LDS and selected there, once per measure
 //   k_svq_long_or, k_svq_long_setup, then per byte 7 .. 0 k_svq_long_hist and
 //   k_svq_long_resolve: §13's launches, segmented.  grid.y is the measure; a
 //   workgroup of _or and _hist takes chunks, each inside one long segment, and
 //   flushes into that segment's bins; _setup and _resolve take one (segment,
 //   measure) each.  All of them read the long segments' count on the device
 //   and leave when there is nothing for them.
+// The select itself, in LDS and as launches, is segmented_select.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,9 +25,8 @@
 
 #include "hip_check.h"
 #include "host_stage.h"
-#include "radix_select.h"
+#include "segmented_select.h"
 #include "service_quantiles.h"
-#include "wave_peel.h"
 
 namespace isim {
 namespace svq {
@@ -35,23 +34,21 @@ namespace {
 
 namespace rs = isim::rs;
 using rs::kBins;
+using rs::kHistThreads;
 using rs::kMaxQ;
+using rs::kResolveThreads;
+using rs::kSelThreads;
+using rs::kUnroll;
+static_assert(rs::kStage == kStage, "the stage is segmented_select.h's");
 static_assert(rs::kClasses == kClasses, "the classes are radix_select.h's");
 
 constexpr uint32_t kThreads = 256;   // clear, count, scatter, or, setup
-constexpr uint32_t kUnroll = 4;      // spans, or elements, per lane in flight
 constexpr uint32_t kMaxGrid = 2048;  // count and scatter stride past it
 constexpr uint32_t kScanThreads = 1024;
-constexpr uint32_t kSelThreads = 512;
-constexpr uint32_t kSelWaves = kSelThreads / 64;
 constexpr uint32_t kSelMaxGrid = 512;  // two workgroups per CU by LDS: 48 KB of bins + 28 KB of stage + 1.2 KB of state
-constexpr uint32_t kHistThreads = 512;  // three workgroups of 48 KB LDS per CU
 constexpr uint32_t kHistWaves = kHistThreads / 64;
 constexpr uint32_t kHistMaxGrid = 1024;  // per measure
-constexpr uint32_t kResolveThreads = 64 * kMaxQ;
 static_assert(kChunk % (kHistThreads * kUnroll) == 0 && kChunk % kThreads == 0, "a chunk is whole steps of a workgroup");
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct Head {
   uint32_t ticket;    // k_svq_short: the next service
@@ -70,10 +67,6 @@ struct Slot {
 };
 static_assert(sizeof(Slot) == kSlotBytes, "isim_service_quantiles_workspace_bytes is pinned");
 
-struct Ppm {
-  uint32_t v[kMaxQ];
-};
-
 struct SK {
   const uint64_t *off, *info;
   const isim_des_span *spans;
@@ -91,9 +84,8 @@ __device__ __forceinline__ uint64_t span_count(const SK &k) {
 }
 
 __global__ __launch_bounds__(kThreads) void k_svq_clear(uint32_t *a, uint64_t na, uint32_t *b, uint64_t nb) {
-  const uint64_t stride = (uint64_t)gridDim.x * kThreads;
-  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < na; i += stride) a[i] = 0;
-  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < nb; i += stride) b[i] = 0;
+  rs::clear_words<kThreads>(a, na);
+  rs::clear_words<kThreads>(b, nb);
 }
 
 // a wave's kUnroll * 64 consecutive spans from `base`: per span the key 2 * service + code (kNone past n or
@@ -153,26 +145,6 @@ __global__ __launch_bounds__(kThreads) void k_svq_count(SK k) {
   }
 }
 
-// exclusive scan of v over the workgroup (kScanThreads); total: the sum
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *s_wave, uint32_t lane, uint32_t wave, uint32_t &total) {
-  uint32_t incl = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(incl, d, 64);
-    if ((int)lane >= d) incl += up;
-  }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-  for (uint32_t w = 0; w < kScanThreads / 64; ++w) {
-    const uint32_t x = s_wave[w];
-    before += w < wave ? x : 0u;
-    total += x;
-  }
-  __syncthreads();  // s_wave is rewritten by the next scan
-  return before + incl - v;
-}
-
 // One workgroup, a service per thread and tile: the exclusive scan of the counts into the segment offsets and
 // the scatter cursors; the long segments get a slot each, in service order, and the first of their chunks.
 // The counts are of at most cap spans, so no more than n_slots segments are long.
@@ -189,9 +161,10 @@ __global__ __launch_bounds__(kScanThreads) void k_svq_scan(const uint32_t *__res
     const uint32_t n = n200 + n500;
     const bool is_long = n > kStage;
     uint32_t t_elem, t_long, t_chunk;
-    const uint32_t e = c_elem + block_scan(n, s_wave, lane, wave, t_elem);
-    const uint32_t l = c_long + block_scan(is_long ? 1u : 0u, s_wave, lane, wave, t_long);
-    const uint32_t c = c_chunk + block_scan(is_long ? (n - 1) / kChunk + 1 : 0u, s_wave, lane, wave, t_chunk);
+    const uint32_t e = c_elem + rs::block_scan<kScanThreads>(n, s_wave, lane, wave, t_elem);
+    const uint32_t l = c_long + rs::block_scan<kScanThreads>(is_long ? 1u : 0u, s_wave, lane, wave, t_long);
+    const uint32_t c =
+        c_chunk + rs::block_scan<kScanThreads>(is_long ? (n - 1) / kChunk + 1 : 0u, s_wave, lane, wave, t_chunk);
     if (live) {
       off[2 * s] = cur[2 * s] = e;
       off[2 * s + 1] = cur[2 * s + 1] = e + n200;
@@ -216,22 +189,6 @@ __global__ __launch_bounds__(kScanThreads) void k_svq_scan(const uint32_t *__res
   }
 }
 
-// The peel of the counts (rs::wave_add) for the cursors: the leader claims a run of positions
-// for the lanes that share its key and each takes the one of its rank among them.
-__device__ __forceinline__ uint32_t wave_claim(uint32_t *cur, uint32_t key, uint32_t lane) {
-  uint32_t pos = 0;
-  dev::wave_peel<dev::kPeelAll>(
-      key, kNone,
-      [&](uint32_t k0, unsigned long long m, int lead) {
-        uint32_t first = 0;
-        if ((int)lane == lead) first = atomicAdd(&cur[k0], (uint32_t)__popcll(m));
-        first = (uint32_t)__builtin_amdgcn_readlane((int)first, lead);
-        if (key == k0) pos = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      },
-      [&](uint32_t k) { pos = atomicAdd(&cur[k], 1u); });
-  return pos;
-}
-
 // Pass 2: the three measures of each span to its service's segment (its 200s, then its 500s).  A position
 // past cap cannot come from counts and cursors of the same spans; were the spans changed under the call,
 // nothing is written outside the segment arrays.
@@ -247,7 +204,7 @@ __global__ __launch_bounds__(kThreads) void k_svq_scatter(SK k) {
     load_keys(k, n, base, lane, key, val, refused);
 #pragma unroll
     for (uint32_t u = 0; u < kUnroll; ++u) {
-      const uint32_t pos = wave_claim(k.cur, key[u], lane);
+      const uint32_t pos = dev::wave_claim(k.cur, key[u], kNone, lane);
       if (key[u] != kNone && pos < k.cap) {
 #pragma unroll
         for (uint32_t m = 0; m < kMeasures; ++m) k.seg[m * k.cap + pos] = val[u][m];
@@ -266,25 +223,17 @@ struct SelArgs {
   uint32_t *bins;           // [n_slots][kMeasures][kClasses][n_q][kBins]
   unsigned long long *out;  // [n_services][kMeasures][kClasses][1 + n_q]
   uint32_t n_services, n_q, n_slots;
-  Ppm ppm;
-};
-
-// The select's state of a workgroup's segment (radix_select.h); the ticket is sel.owner_word.
-struct SelState {
-  rs::State<uint32_t> sel;
-  unsigned long long any[kSelWaves];  // per wave: OR of the segment's values
+  rs::Ppm ppm;
 };
 
 // The short segments.  A workgroup claims services through the ticket until none is left.  An empty service
-// gets its zeros, a long one is the long kernels'.  Otherwise, per measure, the segment is staged in LDS, its
-// OR gives the top byte and from there down each digit is a histogram pass, a resolve (a wave per (class,
-// quantile)) and a regroup.  After byte 0 the prefixes are the values.
+// gets its zeros, a long one is the long kernels'.  Otherwise, per measure, the segment is staged in LDS and
+// selected there (segmented_select.h); the ticket is s.sel.owner_word.
 __global__ __launch_bounds__(kSelThreads) void k_svq_short(SelArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t hist[kClasses * kMaxQ * kBins];
   __shared__ unsigned long long s_stage[kStage];
-  __shared__ SelState s;
-  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-  const uint32_t n_q = a.n_q, ow = 1u + n_q;
+  __shared__ rs::SelState s;
+  const uint32_t t = threadIdx.x, ow = 1u + a.n_q;
   for (;;) {
     __syncthreads();  // the previous segment's state has been read
     if (t == 0) s.sel.owner_word = atomicAdd(&a.head->ticket, 1u);
@@ -309,60 +258,8 @@ __global__ __launch_bounds__(kSelThreads) void k_svq_short(SelArgs a) {
     if (n_seg > kStage || astray) continue;
     for (uint32_t m = 0; m < kMeasures; ++m) {
       __syncthreads();  // the previous measure's state has been read
-      const unsigned long long *seg = a.seg + m * a.cap + off;
-      unsigned long long *om = out + (uint64_t)m * kClasses * ow;
-      unsigned long long any = 0;
-      for (uint32_t i = t; i < n_seg; i += kSelThreads) {
-        const unsigned long long v = seg[i];
-        s_stage[i] = v;
-        any |= v;
-      }
-      for (int d = 32; d; d >>= 1) any |= __shfl_xor(any, d, 64);
-      if (lane == 0) s.any[wave] = any;
-      if (t < kClasses * kMaxQ) {
-        const uint32_t c = t / kMaxQ, i = t % kMaxQ;
-        const uint32_t n_c = c == ISIM_Q_ALL ? n_seg : c == ISIM_Q_200 ? n200 : n500;
-        rs::init(s.sel, c, i, n_q, n_c, a.ppm.v);
-        if (i == 0) om[c * ow] = n_c;
-      }
-      __syncthreads();
-      any = 0;
-      for (uint32_t w = 0; w < kSelWaves; ++w) any |= s.any[w];
-
-      for (int byte = rs::top_byte(any); byte >= 0; --byte) {
-        const uint32_t ng_all = min(s.sel.ngrp[ISIM_Q_ALL], n_q), ng_200 = min(s.sel.ngrp[ISIM_Q_200], n_q),
-                       ng_500 = min(s.sel.ngrp[ISIM_Q_500], n_q);
-        for (uint32_t i = t; i < ng_all * kBins; i += kSelThreads) hist[i] = 0;
-        for (uint32_t i = t; i < ng_200 * kBins; i += kSelThreads) hist[ISIM_Q_200 * kMaxQ * kBins + i] = 0;
-        for (uint32_t i = t; i < ng_500 * kBins; i += kSelThreads) hist[ISIM_Q_500 * kMaxQ * kBins + i] = 0;
-        __syncthreads();
-        // a wave takes 64 * kUnroll consecutive values per step; the loop bound is wave-uniform
-        for (uint32_t base = wave * (64 * kUnroll); base < n_seg; base += kSelWaves * (64 * kUnroll)) {
-#pragma unroll
-          for (uint32_t u = 0; u < kUnroll; ++u) {
-            const uint32_t i = base + u * 64 + lane;
-            rs::count_key(hist, i < n_seg ? s_stage[i] : 0, i < n_seg, byte, i < n200 ? ISIM_Q_200 : ISIM_Q_500,
-                          s.sel.gprefix, ng_all, ng_200, ng_500, lane);
-          }
-        }
-        __syncthreads();
-        for (uint32_t task = wave; task < kClasses * n_q; task += kSelWaves) {  // wave-uniform
-          const uint32_t c = task / n_q, i = task % n_q;
-          const uint32_t k = s.sel.k[c][i];
-          if (!k) continue;  // empty class
-          const uint32_t g = min(s.sel.grp[c][i], n_q - 1);
-          const u32x4 b = *reinterpret_cast<const u32x4 *>(hist + (c * kMaxQ + g) * kBins + lane * 4);
-          uint32_t digit, below;
-          if (rs::resolve<uint32_t>(b.x, b.y, b.z, b.w, k, lane, digit, below)) rs::take_digit(s.sel, c, i, digit, k, below);
-        }
-        __syncthreads();
-        if (t < kClasses) rs::regroup(s.sel, t, n_q);
-        __syncthreads();
-      }
-      if (t < kClasses * kMaxQ && t % kMaxQ < n_q) {
-        const uint32_t c = t / kMaxQ, i = t % kMaxQ;
-        om[c * ow + 1 + i] = s.sel.k[c][i] ? s.sel.prefix[c][i] : 0;
-      }
+      rs::select_segment<true>(hist, s_stage, s, a.seg + m * a.cap + off, n_seg, n200, true, a.n_q, a.ppm,
+                         out + (uint64_t)m * kClasses * ow);
     }
   }
 }
@@ -421,27 +318,19 @@ __global__ __launch_bounds__(kThreads) void k_svq_long_setup(SelArgs a) {
   Slot &x = a.slots[slot];
   const uint32_t n_q = a.n_q, ow = 1u + n_q;
   unsigned long long *om = a.out + ((uint64_t)x.svc * kMeasures + m) * kClasses * ow;
-  if (t < kClasses * kMaxQ) {
-    const uint32_t c = t / kMaxQ, i = t % kMaxQ;
-    const uint32_t n_c = c == ISIM_Q_ALL ? x.n200 + x.n500 : c == ISIM_Q_200 ? x.n200 : x.n500;
-    rs::init(x.st[m], c, i, n_q, n_c, a.ppm.v);
-    if (i == 0) om[c * ow] = n_c;
-  }
+  rs::setup(x.st[m], t, n_q, x.n200 + x.n500, x.n200, x.n500, a.ppm, om);
   if (t == 0) x.st[m].owner_word = (uint32_t)rs::top_byte(x.any[m]);
   const uint32_t words = kClasses * n_q * kBins;
   uint32_t *bins = a.bins + ((uint64_t)slot * kMeasures + m) * words;
   for (uint32_t i = t; i < words; i += kThreads) bins[i] = 0;
 }
 
-// Digit pass `byte` of measure blockIdx.y over the long segments: a workgroup takes chunks; per chunk, per
-// (class, group) of its segment a 256-bin histogram of that byte over the elements whose higher bytes equal
-// the group's prefix, in LDS, and one flush into the segment's bins.
+// Digit pass `byte` of measure blockIdx.y over the long segments: a workgroup takes chunks, each a
+// rs::hist_pass into its segment's bins.
 __global__ __launch_bounds__(kHistThreads) void k_svq_long_hist(SelArgs a, int byte) {
-  __shared__ uint32_t hist[kClasses * kMaxQ * kBins];
-  __shared__ uint64_t s_prefix[kClasses][kMaxQ];
-  __shared__ uint32_t s_ngrp[kClasses];
-  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6, m = blockIdx.y;
-  const uint32_t n_long = a.head->n_long, n_chunks = a.head->n_chunks, n_q = a.n_q;
+  __shared__ rs::HistLds lds;
+  const uint32_t wave = threadIdx.x >> 6, m = blockIdx.y;
+  const uint32_t n_long = a.head->n_long, n_chunks = a.head->n_chunks;
   for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {  // workgroup-uniform
     const uint32_t slot = find_slot(a.slots, n_long, chunk);
     const Slot &x = a.slots[slot];
@@ -449,79 +338,25 @@ __global__ __launch_bounds__(kHistThreads) void k_svq_long_hist(SelArgs a, int b
     uint32_t begin, end;
     if (!chunk_range(x, chunk, a.cap, begin, end)) continue;
     __syncthreads();  // the previous chunk's flush has read the bins
-    if (t < kClasses) s_ngrp[t] = min(x.st[m].ngrp[t], n_q);
-    if (t < kClasses * kMaxQ) s_prefix[t / kMaxQ][t % kMaxQ] = x.st[m].gprefix[t / kMaxQ][t % kMaxQ];
-    __syncthreads();
-    uint32_t ngrp[kClasses];
-    for (uint32_t c = 0; c < kClasses; ++c) {
-      ngrp[c] = s_ngrp[c];
-      for (uint32_t i = t; i < ngrp[c] * kBins; i += kHistThreads) hist[c * kMaxQ * kBins + i] = 0;
-    }
-    __syncthreads();
-    const unsigned long long *seg = a.seg + m * a.cap + x.off;
-    const uint32_t n200 = x.n200;
-    // a wave takes 64 * kUnroll consecutive elements per step; the loop bound is wave-uniform
-    for (uint32_t base = begin + wave * (64 * kUnroll); base < end; base += kHistWaves * (64 * kUnroll)) {
-      unsigned long long key[kUnroll];
-#pragma unroll
-      for (uint32_t u = 0; u < kUnroll; ++u) {
-        const uint32_t i = base + u * 64 + lane;
-        key[u] = i < end ? seg[i] : 0;
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < kUnroll; ++u) {
-        const uint32_t i = base + u * 64 + lane;
-        rs::count_key(hist, key[u], i < end, byte, i < n200 ? ISIM_Q_200 : ISIM_Q_500, s_prefix, ngrp[ISIM_Q_ALL],
-                      ngrp[ISIM_Q_200], ngrp[ISIM_Q_500], lane);
-      }
-    }
-    __syncthreads();
-    uint32_t *bins = a.bins + ((uint64_t)slot * kMeasures + m) * kClasses * n_q * kBins;
-    for (uint32_t c = 0; c < kClasses; ++c)
-      for (uint32_t i = t; i < ngrp[c] * kBins; i += kHistThreads) {
-        const uint32_t v = hist[c * kMaxQ * kBins + i];
-        if (v) atomicAdd(&bins[c * n_q * kBins + i], v);
-      }
+    const auto keys = [&] {
+      const unsigned long long *seg = a.seg + m * a.cap + x.off;
+      const uint32_t n200 = x.n200;
+      return [=](uint32_t i, bool live) { return rs::Key{live ? seg[i] : 0, rs::seg_class(i, n200)}; };
+    };
+    // a wave takes 64 * kUnroll consecutive elements per step
+    rs::hist_pass(lds, x.st[m], a.n_q, byte, begin + wave * (64 * kUnroll), end, kHistWaves * (64 * kUnroll), keys,
+                  a.bins + ((uint64_t)slot * kMeasures + m) * kClasses * a.n_q * kBins);
   }
 }
 
-// After digit pass `byte`, one workgroup per (long segment, measure): the resolve per (class, quantile), wave
-// i taking quantile i of every class, then the regroup, and the bins are cleared.  After byte 0 the prefixes
-// are the values.
+// After digit pass `byte`, one workgroup per (long segment, measure): rs::resolve_pass.
 __global__ __launch_bounds__(kResolveThreads) void k_svq_long_resolve(SelArgs a, int byte) {
-  const uint32_t t = threadIdx.x, lane = t & 63u, i = t >> 6, slot = blockIdx.x, m = blockIdx.y;
+  const uint32_t slot = blockIdx.x, m = blockIdx.y;
   if (slot >= a.head->n_long) return;  // workgroup-uniform
   Slot &x = a.slots[slot];
   rs::State<uint32_t> &st = x.st[m];
-  const uint32_t n_q = a.n_q, ow = 1u + n_q;
-  const int top = (int)st.owner_word;
-  if (byte <= top) {
-    uint32_t *bins = a.bins + ((uint64_t)slot * kMeasures + m) * kClasses * n_q * kBins;
-    if (i < n_q) {
-      for (uint32_t c = 0; c < kClasses; ++c) {
-        const uint32_t k = st.k[c][i];
-        if (!k) continue;  // empty class
-        const uint32_t g = min(st.grp[c][i], n_q - 1);
-        const uint32_t *b = bins + (c * n_q + g) * kBins + lane * 4;  // they sum to at most the segment's length
-        uint32_t digit, below;
-        if (rs::resolve<uint32_t>(b[0], b[1], b[2], b[3], k, lane, digit, below)) rs::take_digit(st, c, i, digit, k, below);
-      }
-    }
-    __syncthreads();  // every wave has read its bins and written its prefix
-    if (t < kClasses) rs::regroup(st, t, n_q);
-    for (uint32_t w = t; w < kClasses * n_q * kBins; w += kResolveThreads) bins[w] = 0;
-  }
-  if (byte == 0) {
-    __syncthreads();
-    if (t < kClasses * kMaxQ && t % kMaxQ < n_q) {
-      const uint32_t c = t / kMaxQ, q = t % kMaxQ;
-      a.out[(((uint64_t)x.svc * kMeasures + m) * kClasses + c) * ow + 1 + q] = st.k[c][q] ? st.prefix[c][q] : 0;
-    }
-  }
-}
-
-uint32_t grid_for(uint64_t items, uint64_t per_workgroup, uint32_t cap) {
-  return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + per_workgroup - 1) / per_workgroup, 1), cap);
+  rs::resolve_pass(st, a.bins + ((uint64_t)slot * kMeasures + m) * kClasses * a.n_q * kBins, a.n_q, byte,
+                   (int)st.owner_word, a.out + ((uint64_t)x.svc * kMeasures + m) * kClasses * (1u + a.n_q));
 }
 
 }  // namespace
@@ -532,7 +367,7 @@ int launch(uint32_t n_services, const uint32_t *q_ppm, uint32_t n_q, const uint6
   const hipStream_t s = (hipStream_t)stream;
   const uint64_t words = table_words(n_services, n_q);
   if (cap_spans == 0) {  // no span: zeros
-    hipLaunchKernelGGL(k_svq_clear, dim3(grid_for(2 * words, kThreads * 4, kMaxGrid)), dim3(kThreads), 0, s,
+    hipLaunchKernelGGL(k_svq_clear, dim3(rs::grid_for(2 * words, kThreads * 4, kMaxGrid)), dim3(kThreads), 0, s,
                        (uint32_t *)d_out, 2 * words, (uint32_t *)nullptr, (uint64_t)0);
     ISIM_HIPCHK(hipGetLastError());
     return ISIM_OK;
@@ -561,13 +396,13 @@ int launch(uint32_t n_services, const uint32_t *q_ppm, uint32_t n_q, const uint6
   a.n_services = n_services;
   a.n_q = n_q;
   a.n_slots = (uint32_t)l.n_slots;
-  for (uint32_t i = 0; i < n_q; ++i) a.ppm.v[i] = q_ppm[i];
+  a.ppm = rs::ppm_of(q_ppm, n_q);
 
   // the head and the counts, contiguous from the workspace's start, and the table's header (every clear is a kernel)
   const uint64_t clear_words = l.cnt / 4 + l.counters;
-  hipLaunchKernelGGL(k_svq_clear, dim3(grid_for(clear_words, kThreads * 4, kMaxGrid)), dim3(kThreads), 0, s,
+  hipLaunchKernelGGL(k_svq_clear, dim3(rs::grid_for(clear_words, kThreads * 4, kMaxGrid)), dim3(kThreads), 0, s,
                      (uint32_t *)ws, clear_words, (uint32_t *)k.hdr, (uint64_t)2 * ISIM_SVQ_HEADER_WORDS);
-  const uint32_t grid = grid_for(cap_spans, kThreads * kUnroll, kMaxGrid);
+  const uint32_t grid = rs::grid_for(cap_spans, kThreads * kUnroll, kMaxGrid);
   hipLaunchKernelGGL(k_svq_count, dim3(grid), dim3(kThreads), 0, s, k);
   hipLaunchKernelGGL(k_svq_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t *)k.cnt, (uint32_t *)(ws + l.off),
                      k.cur, n_services, a.slots, a.n_slots, a.head);
@@ -575,7 +410,7 @@ int launch(uint32_t n_services, const uint32_t *q_ppm, uint32_t n_q, const uint6
   hipLaunchKernelGGL(k_svq_short, dim3(std::min(n_services, kSelMaxGrid)), dim3(kSelThreads), 0, s, a);
   if (a.n_slots) {  // cap_spans allows a long segment: the passes are issued whatever the spans are
     const uint64_t max_chunks = cap_spans / kChunk + a.n_slots;
-    const dim3 chunks(grid_for(max_chunks, 1, kHistMaxGrid), kMeasures), segs(a.n_slots, kMeasures);
+    const dim3 chunks(rs::grid_for(max_chunks, 1, kHistMaxGrid), kMeasures), segs(a.n_slots, kMeasures);
     hipLaunchKernelGGL(k_svq_long_or, chunks, dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(k_svq_long_setup, segs, dim3(kThreads), 0, s, a);
     for (int byte = 7; byte >= 0; --byte) {

@@ -15,10 +15,9 @@
 #include "../../include/isim.h"
 #include "host_stage.h"
 #include "quantile_rank.h"
-#include "radix_select.h"
+#include "segmented_select.h"
 #include "timeline_row.h"
 #include "trace_rec_dev.h"
-#include "wave_peel.h"
 
 namespace {
 
@@ -27,23 +26,21 @@ using isim::dev::rec4;
 using rs::kBins;
 using rs::kClasses;
 using rs::kMaxQ;
+using rs::kSelThreads;
+using rs::kStage;
+using rs::kUnroll;
+using rs::u32x4;
 
 constexpr uint32_t kThreads = 256;        // count, scatter, clear
-constexpr uint32_t kUnroll = 4;           // records per lane in flight
 constexpr uint32_t kMaxGrid = 2048;       // count and scatter stride past it
 constexpr uint32_t kScanThreads = 1024;
 constexpr uint32_t kScanTile = kScanThreads * 4;
-constexpr uint32_t kSelThreads = 512;
-constexpr uint32_t kSelWaves = kSelThreads / 64;
 constexpr uint32_t kSelMaxGrid = 512;     // two workgroups per CU by LDS
-constexpr uint32_t kStage = 3584;         // latencies of a row kept in LDS (28 KB): with the 48 KB of bins two workgroups share a CU
 constexpr uint64_t kMaxRecords = 0xFFFFFFFFull;  // u32 counters, offsets and ranks
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint64_t kHeadBytes = 256;      // the row ticket
 
 int tfail(const std::string &msg) { return isim::set_error(ISIM_EINVAL, msg); }
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // The workspace: the ticket, then three u32 arrays of one word per (row, code)
 // (counts, segment offsets, scatter cursors), then the n latencies by row.
@@ -77,8 +74,7 @@ struct TqArgs {
 };
 
 __global__ __launch_bounds__(kThreads) void k_tlq_clear(uint32_t *words, uint64_t n_words) {
-  const uint64_t stride = (uint64_t)gridDim.x * kThreads;
-  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n_words; i += stride) words[i] = 0;
+  rs::clear_words<kThreads>(words, n_words);
 }
 
 // a wave's kUnroll * 64 consecutive records from `base`: per record the key
@@ -100,22 +96,6 @@ __device__ __forceinline__ void load_keys(const TqArgs &a, uint64_t base, uint32
     const uint64_t c = isim::dev::completion(arr[u], lat[u]);
     key[u] = base + u * 64 + lane < a.n ? isim::tl::row_of(a, c) * 2u + isim::dev::code(r[u]) : kNone;
   }
-}
-
-// The peel of the counts (rs::wave_add) for the cursors: the leader claims a run of positions
-// for the lanes that share its key and each takes the one of its rank among them.
-__device__ __forceinline__ uint32_t wave_claim(uint32_t *cur, uint32_t key, uint32_t lane) {
-  uint32_t pos = 0;
-  isim::dev::wave_peel<isim::dev::kPeelAll>(
-      key, kNone,
-      [&](uint32_t k0, unsigned long long m, int lead) {
-        uint32_t first = 0;
-        if ((int)lane == lead) first = atomicAdd(&cur[k0], (uint32_t)__popcll(m));
-        first = (uint32_t)__builtin_amdgcn_readlane((int)first, lead);
-        if (key == k0) pos = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      },
-      [&](uint32_t k) { pos = atomicAdd(&cur[k], 1u); });
-  return pos;
 }
 
 // Pass 1: records per (row, code).
@@ -150,21 +130,8 @@ __global__ __launch_bounds__(kScanThreads) void k_tlq_scan(const uint32_t *__res
     if (i + 1 >= n_counters) v.y = 0;
     if (i + 2 >= n_counters) v.z = 0;
     if (i + 3 >= n_counters) v.w = 0;
-    const uint32_t sum = v.x + v.y + v.z + v.w;
-    uint32_t incl = sum;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, 64);
-      if ((int)lane >= d) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (uint32_t w = 0; w < kScanThreads / 64; ++w) {
-      const uint32_t x = s_wave[w];
-      before += w < wave ? x : 0u;
-      total += x;
-    }
-    const uint32_t e0 = carry + before + incl - sum;
+    uint32_t total;
+    const uint32_t e0 = carry + rs::block_scan<kScanThreads>(v.x + v.y + v.z + v.w, s_wave, lane, wave, total);
     const u32x4 e{e0, e0 + v.x, e0 + v.x + v.y, e0 + v.x + v.y + v.z};
     if (i + 3 < n_counters) {
       *reinterpret_cast<u32x4 *>(off + i) = e;
@@ -175,7 +142,6 @@ __global__ __launch_bounds__(kScanThreads) void k_tlq_scan(const uint32_t *__res
       if (i + 2 < n_counters) off[i + 2] = cur[i + 2] = e.z;
     }
     carry += total;
-    __syncthreads();  // s_wave is rewritten by the next tile
   }
 }
 
@@ -192,7 +158,7 @@ __global__ __launch_bounds__(kThreads) void k_tlq_scatter(TqArgs a) {
     load_keys(a, base, lane, key, lat);
 #pragma unroll
     for (uint32_t u = 0; u < kUnroll; ++u) {
-      const uint32_t pos = wave_claim(a.cur, key[u], lane);
+      const uint32_t pos = isim::dev::wave_claim(a.cur, key[u], kNone, lane);
       if (key[u] != kNone && pos < a.n) a.seg[pos] = lat[u];
     }
   }
@@ -205,52 +171,17 @@ struct SelArgs {
   uint32_t *ticket;
   unsigned long long *out;         // [rows][3][1 + n_q]
   uint32_t rows, n_q;
-  uint32_t ppm[kMaxQ];
+  rs::Ppm ppm;
 };
-
-// The select's state of a workgroup's row (radix_select.h); the row's ticket is sel.owner_word,
-// which keeps the struct, and with it the kernel's LDS, at its size.
-struct SelState {
-  rs::State<uint32_t> sel;
-  unsigned long long any[kSelWaves];  // per wave: OR of the row's latencies
-};
-
-// One digit of a row: per (class, group) the 256-bin histogram of byte `byte`
-// over the latencies whose higher bytes equal the group's prefix.  Element i of
-// the segment is a 200 below n200, else a 500.
-template <bool STAGED>
-__device__ __forceinline__ void digit_pass(uint32_t *hist, const SelState &s, const unsigned long long *stage,
-                                           const unsigned long long *seg, uint32_t n_row, uint32_t n200, int byte,
-                                           uint32_t ng_all, uint32_t ng_200, uint32_t ng_500, uint32_t lane,
-                                           uint32_t wave) {
-  // a wave takes 64 * kUnroll consecutive latencies per step; the loop bound is wave-uniform
-  for (uint64_t base = (uint64_t)wave * (64 * kUnroll); base < n_row; base += (uint64_t)kSelWaves * (64 * kUnroll)) {
-    unsigned long long key[kUnroll];
-#pragma unroll
-    for (uint32_t u = 0; u < kUnroll; ++u) {
-      const uint64_t i = base + u * 64 + lane;
-      key[u] = i < n_row ? (STAGED ? stage[i] : seg[i]) : 0;
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < kUnroll; ++u) {
-      const uint64_t i = base + u * 64 + lane;
-      rs::count_key(hist, key[u], i < n_row, byte, i < n200 ? ISIM_Q_200 : ISIM_Q_500, s.sel.gprefix, ng_all, ng_200,
-                    ng_500, lane);
-    }
-  }
-}
 
 // The select.  A workgroup claims rows through the ticket until none is left.
-// An empty row gets its zeros; otherwise the row's OR gives the top byte and
-// from there down each digit is a histogram pass, a resolve (a wave per
-// (class, quantile)) and a regroup (radix_select.h).  After byte 0 the
-// prefixes are the values.
+// An empty row gets its zeros, any other the select of segmented_select.h,
+// staged in LDS while it fits; the ticket is s.sel.owner_word.
 __global__ __launch_bounds__(kSelThreads) void k_tlq_select(SelArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t hist[kClasses * kMaxQ * kBins];
   __shared__ unsigned long long s_stage[kStage];
-  __shared__ SelState s;
-  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-  const uint32_t n_q = a.n_q, ow = 1u + n_q;
+  __shared__ rs::SelState s;
+  const uint32_t t = threadIdx.x, ow = 1u + a.n_q;
   for (;;) {
     __syncthreads();  // the previous row's state has been read
     if (t == 0) s.sel.owner_word = atomicAdd(a.ticket, 1u);
@@ -264,58 +195,7 @@ __global__ __launch_bounds__(kSelThreads) void k_tlq_select(SelArgs a) {
       for (uint32_t i = t; i < kClasses * ow; i += kSelThreads) out[i] = 0;
       continue;
     }
-    const unsigned long long *seg = a.seg + a.off[2 * row];
-    const bool staged = n_row <= kStage;
-
-    unsigned long long any = 0;
-    if (staged) {
-      for (uint32_t i = t; i < n_row; i += kSelThreads) {
-        const unsigned long long v = seg[i];
-        s_stage[i] = v;
-        any |= v;
-      }
-    } else {
-      for (uint64_t i = t; i < n_row; i += kSelThreads) any |= seg[i];
-    }
-    for (int d = 32; d; d >>= 1) any |= __shfl_xor(any, d, 64);
-    if (lane == 0) s.any[wave] = any;
-    if (t < kClasses * kMaxQ) {
-      const uint32_t c = t / kMaxQ, i = t % kMaxQ;
-      const uint32_t n_c = c == ISIM_Q_ALL ? n_row : c == ISIM_Q_200 ? n200 : n500;
-      rs::init(s.sel, c, i, n_q, n_c, a.ppm);
-      if (i == 0) out[c * ow] = n_c;
-    }
-    __syncthreads();
-    any = 0;
-    for (uint32_t w = 0; w < kSelWaves; ++w) any |= s.any[w];
-
-    for (int byte = rs::top_byte(any); byte >= 0; --byte) {
-      const uint32_t ng_all = min(s.sel.ngrp[ISIM_Q_ALL], n_q), ng_200 = min(s.sel.ngrp[ISIM_Q_200], n_q),
-                     ng_500 = min(s.sel.ngrp[ISIM_Q_500], n_q);
-      for (uint32_t i = t; i < ng_all * kBins; i += kSelThreads) hist[i] = 0;
-      for (uint32_t i = t; i < ng_200 * kBins; i += kSelThreads) hist[ISIM_Q_200 * kMaxQ * kBins + i] = 0;
-      for (uint32_t i = t; i < ng_500 * kBins; i += kSelThreads) hist[ISIM_Q_500 * kMaxQ * kBins + i] = 0;
-      __syncthreads();
-      if (staged) digit_pass<true>(hist, s, s_stage, seg, n_row, n200, byte, ng_all, ng_200, ng_500, lane, wave);
-      else digit_pass<false>(hist, s, s_stage, seg, n_row, n200, byte, ng_all, ng_200, ng_500, lane, wave);
-      __syncthreads();
-      for (uint32_t task = wave; task < kClasses * n_q; task += kSelWaves) {  // wave-uniform
-        const uint32_t c = task / n_q, i = task % n_q;
-        const uint32_t k = s.sel.k[c][i];
-        if (!k) continue;  // empty class
-        const uint32_t g = min(s.sel.grp[c][i], n_q - 1);
-        const u32x4 b = *reinterpret_cast<const u32x4 *>(hist + (c * kMaxQ + g) * kBins + lane * 4);  // they sum to at most n_row
-        uint32_t digit, below;
-        if (rs::resolve<uint32_t>(b.x, b.y, b.z, b.w, k, lane, digit, below)) rs::take_digit(s.sel, c, i, digit, k, below);
-      }
-      __syncthreads();
-      if (t < kClasses) rs::regroup(s.sel, t, n_q);
-      __syncthreads();
-    }
-    if (t < kClasses * kMaxQ && t % kMaxQ < n_q) {
-      const uint32_t c = t / kMaxQ, i = t % kMaxQ;
-      out[c * ow + 1 + i] = s.sel.k[c][i] ? s.sel.prefix[c][i] : 0;
-    }
+    rs::select_segment<false>(hist, s_stage, s, a.seg + a.off[2 * row], n_row, n200, n_row <= kStage, a.n_q, a.ppm, out);
   }
 }
 
@@ -325,10 +205,6 @@ int check_common(const isim_timeline_params *p, const uint32_t *q_ppm, uint32_t 
   if (const std::string m = isim::q::list_error(q_ppm, n_q); !m.empty()) return tfail(m);
   if (n > kMaxRecords) return tfail("n is above 2^32 - 1");
   return ISIM_OK;
-}
-
-uint32_t grid_for(uint64_t items, uint64_t per_workgroup, uint32_t cap) {
-  return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + per_workgroup - 1) / per_workgroup, 1), cap);
 }
 
 }  // namespace
@@ -361,7 +237,7 @@ int isim_timeline_quantiles_device(const uint64_t *d_arrivals, const isim_trace_
   const uint32_t rows = p->n_windows + 2;
   if (n == 0) {
     const uint64_t words = 2 * ISIM_TLQ_OUT_WORDS(p->n_windows, n_q);  // u32
-    hipLaunchKernelGGL(k_tlq_clear, dim3(grid_for(words, kThreads * 4, kMaxGrid)), dim3(kThreads), 0, s,
+    hipLaunchKernelGGL(k_tlq_clear, dim3(rs::grid_for(words, kThreads * 4, kMaxGrid)), dim3(kThreads), 0, s,
                        (uint32_t *)d_out, words);
     ISIM_HIPCHK(hipGetLastError());
     return ISIM_OK;
@@ -383,13 +259,13 @@ int isim_timeline_quantiles_device(const uint64_t *d_arrivals, const isim_trace_
   sel.out = (unsigned long long *)d_out;
   sel.rows = rows;
   sel.n_q = n_q;
-  for (uint32_t i = 0; i < n_q; ++i) sel.ppm[i] = q_ppm[i];
+  sel.ppm = rs::ppm_of(q_ppm, n_q);
 
   // the ticket and the counts, contiguous from the workspace's start (every clear is a kernel: §13)
   const uint64_t clear_words = l.cnt / 4 + l.counters;
-  hipLaunchKernelGGL(k_tlq_clear, dim3(grid_for(clear_words, kThreads * 4, kMaxGrid)), dim3(kThreads), 0, s,
+  hipLaunchKernelGGL(k_tlq_clear, dim3(rs::grid_for(clear_words, kThreads * 4, kMaxGrid)), dim3(kThreads), 0, s,
                      (uint32_t *)ws, clear_words);
-  const uint32_t grid = grid_for(n, kThreads * kUnroll, kMaxGrid);
+  const uint32_t grid = rs::grid_for(n, kThreads * kUnroll, kMaxGrid);
   hipLaunchKernelGGL(k_tlq_count, dim3(grid), dim3(kThreads), 0, s, a);
   hipLaunchKernelGGL(k_tlq_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t *)a.cnt, (uint32_t *)(ws + l.off),
                      a.cur, (uint32_t)l.counters);

@@ -1,7 +1,8 @@
 // The ballot peel: lanes of a wave that update the same
-// word act once.  Shared by quantile.hip and timeline_quantiles.hip (through
-// radix_select.h's wave_add), and by timeline.hip and service_timeline.hip,
-// which also share the DPP reductions below for their SUM and MAX words.
+// word act once.  Shared by the three quantile selects (radix_select.h's
+// wave_add for their counts, wave_claim for their scatter cursors), and by
+// timeline.hip and service_timeline.hip, which also share the DPP reductions
+// below for their SUM and MAX words.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -38,6 +39,23 @@ __device__ __forceinline__ void wave_peel(uint32_t key, uint32_t none, Shared sh
     rem &= ~m;
   }
   if (key != none) alone(key);
+}
+
+// The peel for cursors: every lane with a key (`none`: no key) gets a position
+// of its own from cur[key]; the leader claims a run of positions for the lanes
+// that share its key and each takes the one of its rank among them.
+__device__ __forceinline__ uint32_t wave_claim(uint32_t *cur, uint32_t key, uint32_t none, uint32_t lane) {
+  uint32_t pos = 0;
+  wave_peel<kPeelAll>(
+      key, none,
+      [&](uint32_t k0, unsigned long long m, int lead) {
+        uint32_t first = 0;
+        if ((int)lane == lead) first = atomicAdd(&cur[k0], (uint32_t)__popcll(m));
+        first = (uint32_t)__builtin_amdgcn_readlane((int)first, lead);
+        if (key == k0) pos = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      },
+      [&](uint32_t k) { pos = atomicAdd(&cur[k], 1u); });
+  return pos;
 }
 
 // ---- wave reductions (all 64 lanes active): row shifts, then the row totals

@@ -24,7 +24,7 @@ U64 = np.uint64
 MAXU = (1 << 64) - 1
 BIT31 = np.uint32(1 << 31)
 Q7 = isim.DEFAULT_Q + (0.0, 1.0)   # the five defaults plus 0 and 10^6 ppm
-KSTAGE = 3584                      # latencies of a row the select keeps in LDS (csrc/timeline_quantiles.hip kStage)
+KSTAGE = 3584                      # latencies of a row the select keeps in LDS (csrc/segmented_select.h kStage)
 
 
 def nearest_rank(n, ppm):
@@ -68,8 +68,10 @@ def check(arr, recs, t0, window, n_windows, q=Q7, note=None):
 def test_restatement_and_stage_constant():
     for n, ppm in ((1, 0), (1, 10**6), (1000, 500_000), (1000, 500_001), (3, 999_000), (70_001, 990_000), (1 << 32, 1)):
         assert nearest_rank(n, ppm) == isim.quantile_rank(n, ppm)
-    src = open(os.path.join(ROOT, "istio-isotope_amd", "csrc", "timeline_quantiles.hip")).read()
+    src = open(os.path.join(ROOT, "istio-isotope_amd", "csrc", "segmented_select.h")).read()
     assert int(re.search(r"constexpr uint32_t kStage = (\d+);", src).group(1)) == KSTAGE
+    abi = open(os.path.join(ROOT, "include", "isim.h")).read()
+    assert int(re.search(r"#define ISIM_SVQ_STAGE (\d+)", abi).group(1)) == KSTAGE
 
 
 @pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1000, 70_001])

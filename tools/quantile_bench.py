@@ -181,7 +181,8 @@ def worker(args):
         raise SystemExit("quantile_bench needs a GPU: it measures, it does not fall back")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    res = {"device": torch.cuda.get_device_name(dev), "warmup": args.warmup,
+    from isim import native
+    res = {"device": torch.cuda.get_device_name(dev), "library": os.path.basename(native.LIB_PATH), "warmup": args.warmup,
            "timing": "HIP events around one call; host clock around the pageable copy and np.partition",
            "entries": [measure(name, args, torch, dev) for name in args.inputs.split(",")]}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -32,12 +32,12 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "istio-isotope_amd"), os.path.join(ROOT
 WINDOWS = {"1s": 10**9, "1ms": 10**6}
 Q = (0.5, 0.75, 0.9, 0.99, 0.999)
 KERNELS = ("k_tlq_clear", "k_tlq_count", "k_tlq_scan", "k_tlq_scatter", "k_tlq_select")
-# -Rpass-analysis=kernel-resource-usage, gfx950 (DESIGN.md §15)
+# -Rpass-analysis=kernel-resource-usage, gfx950 (DESIGN.md §13)
 RESOURCES = {"k_tlq_clear": {"vgprs": 6, "lds_bytes": 0, "scratch_bytes": 0, "waves_per_simd": 8},
              "k_tlq_count": {"vgprs": 32, "lds_bytes": 0, "scratch_bytes": 0, "waves_per_simd": 8},
-             "k_tlq_scan": {"vgprs": 36, "lds_bytes": 64, "scratch_bytes": 0, "waves_per_simd": 8},
+             "k_tlq_scan": {"vgprs": 47, "lds_bytes": 64, "scratch_bytes": 0, "waves_per_simd": 8},
              "k_tlq_scatter": {"vgprs": 36, "lds_bytes": 0, "scratch_bytes": 0, "waves_per_simd": 8},
-             "k_tlq_select": {"vgprs": 111, "lds_bytes": 79056, "scratch_bytes": 0, "waves_per_simd": 4}}
+             "k_tlq_select": {"vgprs": 105, "lds_bytes": 79056, "scratch_bytes": 0, "waves_per_simd": 4}}
 
 
 def parse():
@@ -203,7 +203,9 @@ def worker(args):
     for name in args.inputs.split(","):
         entries += measure(name, args, torch, dev)
         torch.cuda.empty_cache()
-    res = {"device": torch.cuda.get_device_name(dev), "warmup": args.warmup, "quantiles": list(Q),
+    from isim import native
+    res = {"device": torch.cuda.get_device_name(dev), "library": os.path.basename(native.LIB_PATH),
+           "warmup": args.warmup, "quantiles": list(Q),
            "timing": "HIP events around one call; host clock around the numpy sorts; the kernel split from the "
                      "profiler's kernel records of further calls",
            "kernels": RESOURCES, "entries": entries}
