@@ -602,6 +602,69 @@ func (h *Handler) ServiceQuantilesHost(spans []DesSpan, qPpm []uint32) ([]uint64
 	return table, nil
 }
 
+// Per-service percentiles over time (DESIGN §29): per service, timeline row
+// (0 before t0Ns, 1 .. nWindows the windows, nWindows + 1 after; the row of a
+// span's finish), measure and class a cell of 1 + len(qPpm) words as in
+// ServiceQuantiles, then SvqHeaderWords words.
+const (
+	SwqMaxCells = C.ISIM_SWQ_MAX_CELLS
+	SwqWave     = C.ISIM_SWQ_WAVE
+)
+
+// ServiceWindowQuantilesWorkspaceBytes is the workspace the device call
+// (C.isim_service_window_quantiles_device) needs for capSpans spans
+// (isim_service_window_quantiles_workspace_bytes).
+func (h *Handler) ServiceWindowQuantilesWorkspaceBytes(capSpans uint64, nQ int, t0Ns, windowNs uint64, nWindows uint32) (uint64, error) {
+	p := svtParams(t0Ns, windowNs, nWindows)
+	var bytes C.uint64_t
+	if err := lastErr(C.isim_service_window_quantiles_workspace_bytes(h.h, &p, C.uint64_t(capSpans), C.uint32_t(nQ), &bytes)); err != nil {
+		return 0, err
+	}
+	return uint64(bytes), nil
+}
+
+// ServiceWindowQuantiles selects, on GPU `device`, the exact percentiles qPpm
+// of the queue wait, service time and duration of every service and timeline
+// row over spans (every span of a whole tapped batch, in any order) into a new
+// table (isim_service_window_quantiles).
+func (h *Handler) ServiceWindowQuantiles(device int, spans []DesSpan, qPpm []uint32, t0Ns, windowNs uint64, nWindows uint32) ([]uint64, error) {
+	p := svtParams(t0Ns, windowNs, nWindows)
+	var words C.uint64_t
+	if err := lastErr(C.isim_service_window_quantiles_table_words(h.h, &p, C.uint32_t(len(qPpm)), &words)); err != nil {
+		return nil, err
+	}
+	table := make([]uint64, words)
+	var sp *C.isim_des_span
+	if len(spans) > 0 {
+		sp = (*C.isim_des_span)(unsafe.Pointer(&spans[0]))
+	}
+	q := u32ptr(qPpm)
+	if err := lastErr(C.isim_service_window_quantiles(C.int(device), h.h, &p, q, C.uint32_t(len(qPpm)), sp, C.uint64_t(len(spans)), u64ptr(table))); err != nil {
+		return nil, err
+	}
+	return table, nil
+}
+
+// ServiceWindowQuantilesHost is ServiceWindowQuantiles on the CPU
+// (isim_service_window_quantiles_host).
+func (h *Handler) ServiceWindowQuantilesHost(spans []DesSpan, qPpm []uint32, t0Ns, windowNs uint64, nWindows uint32) ([]uint64, error) {
+	p := svtParams(t0Ns, windowNs, nWindows)
+	var words C.uint64_t
+	if err := lastErr(C.isim_service_window_quantiles_table_words(h.h, &p, C.uint32_t(len(qPpm)), &words)); err != nil {
+		return nil, err
+	}
+	table := make([]uint64, words)
+	var sp *C.isim_des_span
+	if len(spans) > 0 {
+		sp = (*C.isim_des_span)(unsafe.Pointer(&spans[0]))
+	}
+	q := u32ptr(qPpm)
+	if err := lastErr(C.isim_service_window_quantiles_host(h.h, &p, q, C.uint32_t(len(qPpm)), sp, C.uint64_t(len(spans)), u64ptr(table))); err != nil {
+		return nil, err
+	}
+	return table, nil
+}
+
 // SelectTraces returns the ids begin + i of the records with a latency of at
 // least minLatencyNs in class cls (C.ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500), in
 // ascending i, at most maxIDs of them, and the number of matching records

@@ -1359,6 +1359,81 @@ ISIM_API int isim_service_quantiles_host(const isim_handler *h, const uint32_t *
 ISIM_API int isim_service_quantiles(int device, const isim_handler *h, const uint32_t *q_ppm, uint32_t n_q,
                                     const isim_des_span *h_spans, uint64_t n_spans, uint64_t *h_out);
 
+/* ---- per-service exact percentiles over time (EXT) ----
+ * histogram_quantile(0.99, service_request_duration_seconds) by service, over
+ * time: for every service and timeline row the exact order statistics of the
+ * three measures of isim_service_quantiles over the isim_des_span records of a
+ * tapped batch (threshold 0: every executed invocation).
+ *
+ * A span is refused by the rule of isim_service_timeline: service >=
+ * n_services, or a <= S <= F does not hold (a = arrival_ns, S = start_ns,
+ * F = finish_ns).  A refused span counts in ISIM_SVQ_H_REFUSED and in nothing
+ * else; the host and the device refuse the same spans.
+ *
+ * Rows: those of isim_timeline under an isim_timeline_params (row 0 "before"
+ * t0_ns, rows 1 .. n_windows the windows, row n_windows + 1 "after"), with the
+ * parameter errors of isim_timeline.  A span belongs to the row in which its
+ * finish F falls, the convention of ISIM_SVT_FINISHED and of
+ * isim_timeline_quantiles (what completes in the row).  t0_ns + n_windows *
+ * window_ns is never formed: any u64 parameters and times are exact.
+ *
+ * Measures ISIM_SVQ_WAIT / ISIM_SVQ_SERVICE / ISIM_SVQ_DURATION and classes
+ * ISIM_Q_ALL / ISIM_Q_200 / ISIM_Q_500 (status bit 0): isim_service_quantiles'.
+ *
+ * The table: u64 [n_services][n_windows + 2][ISIM_SVQ_MEASURES][ISIM_SVQ_CLASSES]
+ * [1 + n_q], then a header of ISIM_SVQ_HEADER_WORDS words (ISIM_SVQ_H_FOLDED,
+ * ISIM_SVQ_H_REFUSED).  Word 0 of a cell is the count N of that service, row
+ * and class (the same for the three measures); word 1 + i is the k-th smallest
+ * value of the measure among them, k = isim_quantile_rank(N, q_ppm[i]); every
+ * word of a cell is 0 where N is 0.  The table is WRITTEN, not added into:
+ * every word is written by the call, and the table may be dirty.  q_ppm: the
+ * rules of isim_latency_quantiles. */
+#define ISIM_SWQ_MAX_CELLS (1u << 20)   /* n_services * (n_windows + 2); at 16 quantiles the table is 1.2 GiB */
+/* The device call ranks a cell of at most ISIM_SWQ_WAVE spans in the registers
+ * of one wave; a cell of up to ISIM_SVQ_STAGE spans is selected in LDS by one
+ * workgroup; a longer one in chunks of ISIM_SVQ_CHUNK, as isim_service_quantiles
+ * does. */
+#define ISIM_SWQ_WAVE 256
+
+/* Every call below returns ISIM_EINVAL, before any HIP call, for what
+ * isim_service_quantiles refuses (the handler, a null argument, the quantile
+ * list, more than ISIM_SVQ_MAX_SPANS spans), for parameters isim_timeline
+ * refuses, and for more than ISIM_SWQ_MAX_CELLS cells. */
+/* host only, no GPU: C * 9 * (1 + n_q) + ISIM_SVQ_HEADER_WORDS with C = n_services * (n_windows + 2) */
+ISIM_API int isim_service_window_quantiles_table_words(const isim_handler *h, const isim_timeline_params *p,
+                                                       uint32_t n_q, uint64_t *words);
+/* host only, no GPU.  With P(x) = x rounded up to a multiple of 256 and C the cells:
+ *   256 + 3 * P(8 * C)                                 per cell: counts, offsets and cursors by (cell, code)
+ *   + P(4 * M)                                         the list of the cells selected in LDS
+ *   + 24 * cap_spans                                   per span: its three measures, scattered by cell
+ *   + L * (ISIM_SVQ_SLOT_BYTES + 9 * n_q * 1024)       per long segment: select states and u32 bins
+ * where M = min(C, cap_spans / (ISIM_SWQ_WAVE + 1)) and L = min(C, cap_spans / (ISIM_SVQ_STAGE + 1)) are the
+ * most cells of either kind cap_spans spans can form. */
+ISIM_API int isim_service_window_quantiles_workspace_bytes(const isim_handler *h, const isim_timeline_params *p,
+                                                           uint64_t cap_spans, uint32_t n_q, uint64_t *bytes);
+/* The table of the spans that a preceding isim_serve_des_spans_device wrote to
+ * d_spans, addressed as isim_service_quantiles_device addresses them (the span
+ * count is read on the device and bounded by cap_spans), on the current
+ * device, asynchronously on hip_stream.  WRITES d_out.  A fixed sequence of
+ * kernels that does not depend on the data: no host synchronisation, no
+ * allocation, graph-capturable from the first call, the workspace may be dirty
+ * (calls that share one must be ordered).  cap_spans 0 writes zeros and needs
+ * no workspace.  Also ISIM_EINVAL: buffers not 8-byte aligned (d_spans 16), a
+ * workspace below isim_service_window_quantiles_workspace_bytes. */
+ISIM_API int isim_service_window_quantiles_device(const isim_handler *h, const isim_timeline_params *p,
+                                                  const uint32_t *q_ppm, uint32_t n_q, const uint64_t *d_off,
+                                                  const isim_des_span *d_spans, uint64_t cap_spans,
+                                                  const uint64_t *d_info, uint64_t *d_out, void *d_workspace,
+                                                  uint64_t workspace_bytes, void *hip_stream);
+/* host only, no GPU: the same table on the CPU over h_spans[0 .. n_spans) (a sort per cell, measure and class) */
+ISIM_API int isim_service_window_quantiles_host(const isim_handler *h, const isim_timeline_params *p,
+                                                const uint32_t *q_ppm, uint32_t n_q, const isim_des_span *h_spans,
+                                                uint64_t n_spans, uint64_t *h_out);
+/* Synchronous convenience: host buffers, on GPU `device`. */
+ISIM_API int isim_service_window_quantiles(int device, const isim_handler *h, const isim_timeline_params *p,
+                                           const uint32_t *q_ppm, uint32_t n_q, const isim_des_span *h_spans,
+                                           uint64_t n_spans, uint64_t *h_out);
+
 #ifdef __cplusplus
 }
 #endif

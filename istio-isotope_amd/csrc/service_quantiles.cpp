@@ -12,8 +12,10 @@ namespace {
 namespace svq = isim::svq;
 int qfail(const std::string &msg) { return isim::set_error(ISIM_EINVAL, "service quantiles: " + msg); }
 
+}  // namespace
+
 // the handler and the number of quantiles; n_services on success
-int check_sizes(const isim_handler *h, uint32_t n_q, uint64_t n_spans, uint64_t &n_services) {
+int isim::svq::check_sizes(const isim_handler *h, uint32_t n_q, uint64_t n_spans, uint64_t &n_services) {
   if (!h) return qfail("null handler");
   if (const int rc = isim::svt::check_handler(h)) return rc;
   if (n_q == 0 || n_q > ISIM_MAX_QUANTILES) return qfail("n_q must be 1.." + std::to_string(ISIM_MAX_QUANTILES));
@@ -22,8 +24,6 @@ int check_sizes(const isim_handler *h, uint32_t n_q, uint64_t n_spans, uint64_t 
   if (n_services > svq::kMaxServices) return qfail("more than 2^30 services");
   return ISIM_OK;
 }
-
-}  // namespace
 
 int isim::svq::check(const isim_handler *h, const uint32_t *q_ppm, uint32_t n_q, uint64_t n_spans,
                      uint64_t &n_services) {
@@ -36,7 +36,7 @@ extern "C" {
 
 int isim_service_quantiles_table_words(const isim_handler *h, uint32_t n_q, uint64_t *words) {
   uint64_t ns = 0;
-  if (const int rc = check_sizes(h, n_q, 0, ns)) return rc;
+  if (const int rc = svq::check_sizes(h, n_q, 0, ns)) return rc;
   if (!words) return qfail("null argument");
   *words = svq::table_words(ns, n_q);
   return ISIM_OK;
@@ -44,7 +44,7 @@ int isim_service_quantiles_table_words(const isim_handler *h, uint32_t n_q, uint
 
 int isim_service_quantiles_workspace_bytes(const isim_handler *h, uint64_t cap_spans, uint32_t n_q, uint64_t *bytes) {
   uint64_t ns = 0;
-  if (const int rc = check_sizes(h, n_q, cap_spans, ns)) return rc;
+  if (const int rc = svq::check_sizes(h, n_q, cap_spans, ns)) return rc;
   if (!bytes) return qfail("null argument");
   *bytes = svq::layout(ns, cap_spans, n_q).total;
   return ISIM_OK;

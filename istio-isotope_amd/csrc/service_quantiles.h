@@ -71,36 +71,39 @@ inline Layout layout(uint64_t n_services, uint64_t cap, uint32_t n_q) {
   return l;
 }
 
-// ---- the host's fold (isim_service_quantiles_host, and tests/cpp/service_quantiles_check.cpp under the
-// sanitizers).  WRITES every word of out [table_words(n_services, n_q)].
-inline void fold_host(uint32_t n_services, const uint32_t *q_ppm, uint32_t n_q, const isim_des_span *spans, uint64_t n,
-                      uint64_t *out) {
-  const uint64_t ow = cell_words(n_q), words = table_words(n_services, n_q);
+// ---- the host's fold of spans into segments of a table [n_segments][kMeasures][kClasses][1 + n_q] and its
+// header: segment_of(span) is the span's segment, kNone for a refused one; a sort per segment, measure and
+// class.  WRITES every word of out [n_segments * kMeasures * kClasses * (1 + n_q) + ISIM_SVQ_HEADER_WORDS].
+template <typename SegmentOf>
+inline void fold_segments(uint64_t n_segments, const uint32_t *q_ppm, uint32_t n_q, const isim_des_span *spans,
+                          uint64_t n, uint64_t *out, SegmentOf segment_of) {
+  const uint64_t ow = cell_words(n_q), words = table_words(n_segments, n_q);
   for (uint64_t i = 0; i < words; ++i) out[i] = 0;
   uint64_t *hdr = out + words - ISIM_SVQ_HEADER_WORDS;
-  // spans per (service, code), then their indices by (service, code)
-  std::vector<uint64_t> off(2 * (uint64_t)n_services + 1, 0);
+  // spans per (segment, code), then their indices by (segment, code)
+  std::vector<uint64_t> off(2 * n_segments + 1, 0);
   for (uint64_t i = 0; i < n; ++i) {
     const isim_des_span &s = spans[i];
-    if (span_refused(n_services, s.arrival_ns, s.start_ns, s.finish_ns, s.service)) {
+    const uint32_t g = segment_of(s);
+    if (g == kNone) {
       hdr[ISIM_SVQ_H_REFUSED] += 1;
       continue;
     }
     hdr[ISIM_SVQ_H_FOLDED] += 1;
-    off[2 * (uint64_t)s.service + (s.status & 1u) + 1] += 1;
+    off[2 * (uint64_t)g + (s.status & 1u) + 1] += 1;
   }
-  for (uint64_t k = 0; k < 2 * (uint64_t)n_services; ++k) off[k + 1] += off[k];
+  for (uint64_t k = 0; k < 2 * n_segments; ++k) off[k + 1] += off[k];
   std::vector<uint64_t> cur(off.begin(), off.end() - 1), idx(hdr[ISIM_SVQ_H_FOLDED]);
   for (uint64_t i = 0; i < n; ++i) {
     const isim_des_span &s = spans[i];
-    if (!span_refused(n_services, s.arrival_ns, s.start_ns, s.finish_ns, s.service))
-      idx[cur[2 * (uint64_t)s.service + (s.status & 1u)]++] = i;
+    const uint32_t g = segment_of(s);
+    if (g != kNone) idx[cur[2 * (uint64_t)g + (s.status & 1u)]++] = i;
   }
   std::vector<uint64_t> v;
-  for (uint32_t s = 0; s < n_services; ++s) {
-    // the class's elements of the service's segment: all, its 200s, its 500s
-    const uint64_t lo[kClasses] = {off[2 * (uint64_t)s], off[2 * (uint64_t)s], off[2 * (uint64_t)s + 1]};
-    const uint64_t hi[kClasses] = {off[2 * (uint64_t)s + 2], off[2 * (uint64_t)s + 1], off[2 * (uint64_t)s + 2]};
+  for (uint64_t s = 0; s < n_segments; ++s) {
+    // the class's elements of the segment: all, its 200s, its 500s
+    const uint64_t lo[kClasses] = {off[2 * s], off[2 * s], off[2 * s + 1]};
+    const uint64_t hi[kClasses] = {off[2 * s + 2], off[2 * s + 1], off[2 * s + 2]};
     for (uint32_t m = 0; m < kMeasures; ++m)
       for (uint32_t c = 0; c < kClasses; ++c) {
         const uint64_t n_c = hi[c] - lo[c];
@@ -111,14 +114,25 @@ inline void fold_host(uint32_t n_services, const uint32_t *q_ppm, uint32_t n_q, 
           v[i] = measure(m, x.arrival_ns, x.start_ns, x.finish_ns);
         }
         std::sort(v.begin(), v.end());
-        uint64_t *cell = out + (((uint64_t)s * kMeasures + m) * kClasses + c) * ow;
+        uint64_t *cell = out + ((s * kMeasures + m) * kClasses + c) * ow;
         cell[0] = n_c;
         for (uint32_t i = 0; i < n_q; ++i) cell[1 + i] = v[q::nearest_rank(n_c, q_ppm[i]) - 1];
       }
   }
 }
 
-// ---- host side (service_quantiles.cpp): the handler, the quantile list and the span bound; n_services on success
+// isim_service_quantiles_host, and tests/cpp/service_quantiles_check.cpp under the sanitizers: a segment per
+// service.  WRITES every word of out [table_words(n_services, n_q)].
+inline void fold_host(uint32_t n_services, const uint32_t *q_ppm, uint32_t n_q, const isim_des_span *spans, uint64_t n,
+                      uint64_t *out) {
+  fold_segments(n_services, q_ppm, n_q, spans, n, out, [n_services](const isim_des_span &s) {
+    return span_refused(n_services, s.arrival_ns, s.start_ns, s.finish_ns, s.service) ? kNone : s.service;
+  });
+}
+
+// ---- host side (service_quantiles.cpp): the handler, the number of quantiles and the span bound, and with
+// them the quantile list; n_services on success
+int check_sizes(const isim_handler *h, uint32_t n_q, uint64_t n_spans, uint64_t &n_services);
 int check(const isim_handler *h, const uint32_t *q_ppm, uint32_t n_q, uint64_t n_spans, uint64_t &n_services);
 
 // ---- device side (service_quantiles.hip): the launches of one checked call

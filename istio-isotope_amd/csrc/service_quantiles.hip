@@ -17,7 +17,9 @@
 //   flushes into that segment's bins; _setup and _resolve take one (segment,
 //   measure) each.  All of them read the long segments' count on the device
 //   and leave when there is nothing for them.
-// The select itself, in LDS and as launches, is segmented_select.h's.
+// The select itself, in LDS and as launches, is segmented_select.h's; the span
+// load, the count, the scatter and the long segments' kernels are
+// span_segments.h's, which service_window_quantiles.hip (§29) shares.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,125 +27,13 @@
 
 #include "hip_check.h"
 #include "host_stage.h"
-#include "segmented_select.h"
-#include "service_quantiles.h"
+#include "span_segments.h"
 
 namespace isim {
 namespace svq {
 namespace {
 
-namespace rs = isim::rs;
-using rs::kBins;
-using rs::kHistThreads;
-using rs::kMaxQ;
-using rs::kResolveThreads;
-using rs::kSelThreads;
-using rs::kUnroll;
-static_assert(rs::kStage == kStage, "the stage is segmented_select.h's");
-static_assert(rs::kClasses == kClasses, "the classes are radix_select.h's");
-
-constexpr uint32_t kThreads = 256;   // clear, count, scatter, or, setup
-constexpr uint32_t kMaxGrid = 2048;  // count and scatter stride past it
 constexpr uint32_t kScanThreads = 1024;
-constexpr uint32_t kSelMaxGrid = 512;  // two workgroups per CU by LDS: 48 KB of bins + 28 KB of stage + 1.2 KB of state
-constexpr uint32_t kHistWaves = kHistThreads / 64;
-constexpr uint32_t kHistMaxGrid = 1024;  // per measure
-static_assert(kChunk % (kHistThreads * kUnroll) == 0 && kChunk % kThreads == 0, "a chunk is whole steps of a workgroup");
-
-struct Head {
-  uint32_t ticket;    // k_svq_short: the next service
-  uint32_t n_long;    // long segments
-  uint32_t n_chunks;  // their chunks
-};
-static_assert(sizeof(Head) <= kHeadBytes, "the head fits its bytes");
-
-// a long segment; the select's top byte of measure m is st[m].owner_word (as int; -1: every value is 0)
-struct Slot {
-  uint32_t svc, chunk0, n200, n500;
-  uint64_t off;  // the segment's first element
-  unsigned long long any[kMeasures];
-  rs::State<uint32_t> st[kMeasures];
-  unsigned char pad[kSlotBytes - 48 - kMeasures * sizeof(rs::State<uint32_t>)];
-};
-static_assert(sizeof(Slot) == kSlotBytes, "isim_service_quantiles_workspace_bytes is pinned");
-
-struct SK {
-  const uint64_t *off, *info;
-  const isim_des_span *spans;
-  uint64_t cap;
-  uint32_t n_services;
-  uint32_t *cnt;            // count: [n_services][2], added to
-  uint32_t *cur;            // scatter: [n_services][2] cursors
-  unsigned long long *seg;  // scatter: [kMeasures][cap]
-  unsigned long long *hdr;  // the table's header
-};
-
-__device__ __forceinline__ uint64_t span_count(const SK &k) {
-  const uint64_t end = k.off[k.info[ISIM_SPAN_WRITTEN]];
-  return end < k.cap ? end : k.cap;
-}
-
-__global__ __launch_bounds__(kThreads) void k_svq_clear(uint32_t *a, uint64_t na, uint32_t *b, uint64_t nb) {
-  rs::clear_words<kThreads>(a, na);
-  rs::clear_words<kThreads>(b, nb);
-}
-
-// a wave's kUnroll * 64 consecutive spans from `base`: per span the key 2 * service + code (kNone past n or
-// refused) and the three measures
-__device__ __forceinline__ void load_keys(const SK &k, uint64_t n, uint64_t base, uint32_t lane, uint32_t (&key)[kUnroll],
-                                          uint64_t (&val)[kUnroll][kMeasures], uint32_t &refused) {
-  uint64_t a[kUnroll], s[kUnroll], f[kUnroll];
-  uint32_t svc[kUnroll], st[kUnroll];
-#pragma unroll
-  for (uint32_t u = 0; u < kUnroll; ++u) {
-    const uint64_t i = base + u * 64 + lane;
-    a[u] = s[u] = f[u] = 0;
-    svc[u] = kNone;
-    st[u] = 0;
-    if (i < n) {
-      const isim_des_span &x = k.spans[i];
-      a[u] = x.arrival_ns;
-      s[u] = x.start_ns;
-      f[u] = x.finish_ns;
-      svc[u] = x.service;
-      st[u] = x.status;
-    }
-  }
-#pragma unroll
-  for (uint32_t u = 0; u < kUnroll; ++u) {
-    const bool live = base + u * 64 + lane < n;
-    const bool bad = span_refused(k.n_services, a[u], s[u], f[u], svc[u]);
-    refused += live && bad ? 1u : 0u;
-    key[u] = live && !bad ? svc[u] * 2u + (st[u] & 1u) : kNone;
-#pragma unroll
-    for (uint32_t m = 0; m < kMeasures; ++m) val[u][m] = measure(m, a[u], s[u], f[u]);
-  }
-}
-
-// Pass 1: spans per (service, code), and the header.
-__global__ __launch_bounds__(kThreads) void k_svq_count(SK k) {
-  const uint64_t n = span_count(k);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t wave = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
-  const uint64_t step = (uint64_t)gridDim.x * (kThreads / 64) * (64 * kUnroll);
-  uint32_t refused = 0, folded = 0;
-  // a wave takes 64 * kUnroll consecutive spans per step; the loop bound is wave-uniform
-  for (uint64_t base = wave * (64 * kUnroll); base < n; base += step) {
-    uint32_t key[kUnroll];
-    uint64_t val[kUnroll][kMeasures];
-    load_keys(k, n, base, lane, key, val, refused);
-#pragma unroll
-    for (uint32_t u = 0; u < kUnroll; ++u) {
-      folded += key[u] != kNone ? 1u : 0u;
-      rs::wave_add(k.cnt, (int)key[u], lane);  // kNone: no bin
-    }
-  }
-  const uint64_t fo = dev::wave_reduce<dev::OpAdd>(folded), re = dev::wave_reduce<dev::OpAdd>(refused);
-  if (lane == 0) {
-    if (fo) atomicAdd(k.hdr + ISIM_SVQ_H_FOLDED, (unsigned long long)fo);
-    if (re) atomicAdd(k.hdr + ISIM_SVQ_H_REFUSED, (unsigned long long)re);
-  }
-}
 
 // One workgroup, a service per thread and tile: the exclusive scan of the counts into the segment offsets and
 // the scatter cursors; the long segments get a slot each, in service order, and the first of their chunks.
@@ -189,43 +79,6 @@ __global__ __launch_bounds__(kScanThreads) void k_svq_scan(const uint32_t *__res
   }
 }
 
-// Pass 2: the three measures of each span to its service's segment (its 200s, then its 500s).  A position
-// past cap cannot come from counts and cursors of the same spans; were the spans changed under the call,
-// nothing is written outside the segment arrays.
-__global__ __launch_bounds__(kThreads) void k_svq_scatter(SK k) {
-  const uint64_t n = span_count(k);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t wave = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
-  const uint64_t step = (uint64_t)gridDim.x * (kThreads / 64) * (64 * kUnroll);
-  uint32_t refused = 0;
-  for (uint64_t base = wave * (64 * kUnroll); base < n; base += step) {
-    uint32_t key[kUnroll];
-    uint64_t val[kUnroll][kMeasures];
-    load_keys(k, n, base, lane, key, val, refused);
-#pragma unroll
-    for (uint32_t u = 0; u < kUnroll; ++u) {
-      const uint32_t pos = dev::wave_claim(k.cur, key[u], kNone, lane);
-      if (key[u] != kNone && pos < k.cap) {
-#pragma unroll
-        for (uint32_t m = 0; m < kMeasures; ++m) k.seg[m * k.cap + pos] = val[u][m];
-      }
-    }
-  }
-}
-
-struct SelArgs {
-  const uint32_t *cnt;            // [n_services][2]
-  const uint32_t *off;            // [n_services][2]
-  const unsigned long long *seg;  // [kMeasures][cap]
-  uint64_t cap;
-  Head *head;
-  Slot *slots;
-  uint32_t *bins;           // [n_slots][kMeasures][kClasses][n_q][kBins]
-  unsigned long long *out;  // [n_services][kMeasures][kClasses][1 + n_q]
-  uint32_t n_services, n_q, n_slots;
-  rs::Ppm ppm;
-};
-
 // The short segments.  A workgroup claims services through the ticket until none is left.  An empty service
 // gets its zeros, a long one is the long kernels'.  Otherwise, per measure, the segment is staged in LDS and
 // selected there (segmented_select.h); the ticket is s.sel.owner_word.
@@ -262,101 +115,6 @@ __global__ __launch_bounds__(kSelThreads) void k_svq_short(SelArgs a) {
                          out + (uint64_t)m * kClasses * ow);
     }
   }
-}
-
-// the long segment that holds chunk (< n_chunks, so n_long >= 1): the last slot whose first chunk is at or before it
-__device__ __forceinline__ uint32_t find_slot(const Slot *slots, uint32_t n_long, uint32_t chunk) {
-  uint32_t lo = 0, hi = n_long;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (slots[mid].chunk0 <= chunk) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// the elements [begin, end) of the slot's segment that are the chunk's; false: none (counts not of these spans)
-__device__ __forceinline__ bool chunk_range(const Slot &x, uint32_t chunk, uint64_t cap, uint32_t &begin, uint32_t &end) {
-  const uint32_t n_seg = x.n200 + x.n500;
-  const uint64_t b = (uint64_t)(chunk - x.chunk0) * kChunk;
-  if (b >= n_seg || x.off + n_seg > cap) return false;
-  begin = (uint32_t)b;
-  end = n_seg - begin > kChunk ? begin + kChunk : n_seg;
-  return true;
-}
-
-// The OR of every long segment's values, per measure (blockIdx.y): the bytes above its top bit are zero.
-__global__ __launch_bounds__(kThreads) void k_svq_long_or(SelArgs a) {
-  __shared__ unsigned long long s_any[kThreads / 64];
-  const uint32_t t = threadIdx.x, m = blockIdx.y;
-  const uint32_t n_long = a.head->n_long, n_chunks = a.head->n_chunks;
-  for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {  // workgroup-uniform
-    const uint32_t slot = find_slot(a.slots, n_long, chunk);
-    Slot &x = a.slots[slot];
-    uint32_t begin, end;
-    if (!chunk_range(x, chunk, a.cap, begin, end)) continue;
-    const unsigned long long *seg = a.seg + m * a.cap + x.off;
-    unsigned long long any = 0;
-    for (uint32_t i = begin + t; i < end; i += kThreads) any |= seg[i];
-    for (int d = 32; d; d >>= 1) any |= __shfl_xor(any, d, 64);
-    __syncthreads();  // the previous chunk's s_any has been read
-    if ((t & 63u) == 0) s_any[t >> 6] = any;
-    __syncthreads();
-    if (t == 0) {
-      any = 0;
-      for (uint32_t w = 0; w < kThreads / 64; ++w) any |= s_any[w];
-      if (any) atomicOr(&x.any[m], any);
-    }
-  }
-}
-
-// One workgroup per (long segment, measure): the ranks from the counts, one group per non-empty class, the
-// top byte, the counts into the table, and the segment's bins cleared.
-__global__ __launch_bounds__(kThreads) void k_svq_long_setup(SelArgs a) {
-  const uint32_t t = threadIdx.x, slot = blockIdx.x, m = blockIdx.y;
-  if (slot >= a.head->n_long) return;  // workgroup-uniform
-  Slot &x = a.slots[slot];
-  const uint32_t n_q = a.n_q, ow = 1u + n_q;
-  unsigned long long *om = a.out + ((uint64_t)x.svc * kMeasures + m) * kClasses * ow;
-  rs::setup(x.st[m], t, n_q, x.n200 + x.n500, x.n200, x.n500, a.ppm, om);
-  if (t == 0) x.st[m].owner_word = (uint32_t)rs::top_byte(x.any[m]);
-  const uint32_t words = kClasses * n_q * kBins;
-  uint32_t *bins = a.bins + ((uint64_t)slot * kMeasures + m) * words;
-  for (uint32_t i = t; i < words; i += kThreads) bins[i] = 0;
-}
-
-// Digit pass `byte` of measure blockIdx.y over the long segments: a workgroup takes chunks, each a
-// rs::hist_pass into its segment's bins.
-__global__ __launch_bounds__(kHistThreads) void k_svq_long_hist(SelArgs a, int byte) {
-  __shared__ rs::HistLds lds;
-  const uint32_t wave = threadIdx.x >> 6, m = blockIdx.y;
-  const uint32_t n_long = a.head->n_long, n_chunks = a.head->n_chunks;
-  for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {  // workgroup-uniform
-    const uint32_t slot = find_slot(a.slots, n_long, chunk);
-    const Slot &x = a.slots[slot];
-    if (byte > (int)x.st[m].owner_word) continue;  // every value is zero in this byte: the prefixes keep a zero digit
-    uint32_t begin, end;
-    if (!chunk_range(x, chunk, a.cap, begin, end)) continue;
-    __syncthreads();  // the previous chunk's flush has read the bins
-    const auto keys = [&] {
-      const unsigned long long *seg = a.seg + m * a.cap + x.off;
-      const uint32_t n200 = x.n200;
-      return [=](uint32_t i, bool live) { return rs::Key{live ? seg[i] : 0, rs::seg_class(i, n200)}; };
-    };
-    // a wave takes 64 * kUnroll consecutive elements per step
-    rs::hist_pass(lds, x.st[m], a.n_q, byte, begin + wave * (64 * kUnroll), end, kHistWaves * (64 * kUnroll), keys,
-                  a.bins + ((uint64_t)slot * kMeasures + m) * kClasses * a.n_q * kBins);
-  }
-}
-
-// After digit pass `byte`, one workgroup per (long segment, measure): rs::resolve_pass.
-__global__ __launch_bounds__(kResolveThreads) void k_svq_long_resolve(SelArgs a, int byte) {
-  const uint32_t slot = blockIdx.x, m = blockIdx.y;
-  if (slot >= a.head->n_long) return;  // workgroup-uniform
-  Slot &x = a.slots[slot];
-  rs::State<uint32_t> &st = x.st[m];
-  rs::resolve_pass(st, a.bins + ((uint64_t)slot * kMeasures + m) * kClasses * a.n_q * kBins, a.n_q, byte,
-                   (int)st.owner_word, a.out + ((uint64_t)x.svc * kMeasures + m) * kClasses * (1u + a.n_q));
 }
 
 }  // namespace
@@ -403,21 +161,12 @@ int launch(uint32_t n_services, const uint32_t *q_ppm, uint32_t n_q, const uint6
   hipLaunchKernelGGL(k_svq_clear, dim3(rs::grid_for(clear_words, kThreads * 4, kMaxGrid)), dim3(kThreads), 0, s,
                      (uint32_t *)ws, clear_words, (uint32_t *)k.hdr, (uint64_t)2 * ISIM_SVQ_HEADER_WORDS);
   const uint32_t grid = rs::grid_for(cap_spans, kThreads * kUnroll, kMaxGrid);
-  hipLaunchKernelGGL(k_svq_count, dim3(grid), dim3(kThreads), 0, s, k);
+  hipLaunchKernelGGL(k_svq_count<ServiceKey>, dim3(grid), dim3(kThreads), 0, s, k, ServiceKey{});
   hipLaunchKernelGGL(k_svq_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t *)k.cnt, (uint32_t *)(ws + l.off),
                      k.cur, n_services, a.slots, a.n_slots, a.head);
-  hipLaunchKernelGGL(k_svq_scatter, dim3(grid), dim3(kThreads), 0, s, k);
+  hipLaunchKernelGGL(k_svq_scatter<ServiceKey>, dim3(grid), dim3(kThreads), 0, s, k, ServiceKey{});
   hipLaunchKernelGGL(k_svq_short, dim3(std::min(n_services, kSelMaxGrid)), dim3(kSelThreads), 0, s, a);
-  if (a.n_slots) {  // cap_spans allows a long segment: the passes are issued whatever the spans are
-    const uint64_t max_chunks = cap_spans / kChunk + a.n_slots;
-    const dim3 chunks(rs::grid_for(max_chunks, 1, kHistMaxGrid), kMeasures), segs(a.n_slots, kMeasures);
-    hipLaunchKernelGGL(k_svq_long_or, chunks, dim3(kThreads), 0, s, a);
-    hipLaunchKernelGGL(k_svq_long_setup, segs, dim3(kThreads), 0, s, a);
-    for (int byte = 7; byte >= 0; --byte) {
-      hipLaunchKernelGGL(k_svq_long_hist, chunks, dim3(kHistThreads), 0, s, a, byte);
-      hipLaunchKernelGGL(k_svq_long_resolve, segs, dim3(kResolveThreads), 0, s, a, byte);
-    }
-  }
+  launch_long(a, cap_spans, s);
   ISIM_HIPCHK(hipGetLastError());
   return ISIM_OK;
 }

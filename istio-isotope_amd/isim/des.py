@@ -309,6 +309,51 @@ class DesHandler:
                                f"{int(h_info[native.DES_SPAN_MATCHES])} traces")
         return ServiceQuantiles(self.handler, q, h_out[:words].copy())
 
+    def service_window_quantiles(self, trace_begin: int, n_traces: int, q=DEFAULT_Q, window_ns: int = 1_000_000,
+                                 n_windows: int = 100, t0_ns: int = 0, device: int = 0, cap_spans: int = None):
+        """The ServiceWindowQuantiles of one batch: the whole batch tapped as service_timeline
+        taps it, its windows given as service_timeline takes them, and the select per (service, row) made on
+        the same stream; only the table comes back.  32-bit rows first, and again wide if the batch asks for
+        it.  Raises if the spans did not fit cap_spans: never a partial table.  Item engine only."""
+        import torch
+        from . import des_spans as ds
+        from .service_window_quantiles import (ServiceWindowQuantiles, service_window_quantiles_device,
+                                               service_window_quantiles_table_words,
+                                               service_window_quantiles_workspace_bytes)
+        q = tuple(q)
+        n_traces = int(n_traces)
+        cap = n_traces * int(self.handler.info.hops_upper) if cap_spans is None else int(cap_spans)
+        words = service_window_quantiles_table_words(self.handler, len(q), window_ns, n_windows, t0_ns)
+        qws_bytes = service_window_quantiles_workspace_bytes(self.handler, cap, len(q), window_ns, n_windows, t0_ns)
+        dev = torch.device("cuda", device)
+        u64 = lambda t: t.cpu().numpy().view(np.uint64)  # noqa: E731
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            z = lambda n: torch.zeros(max(1, n), dtype=torch.int64, device=dev)  # noqa: E731
+            ws = z(self.workspace_bytes(n_traces) // 8 + 1)
+            qws = torch.empty(max(1, qws_bytes // 8 + 1), dtype=torch.int64, device=dev)
+            out = torch.empty(words, dtype=torch.int64, device=dev)
+            for w in [False, True]:
+                stats, table, rec = z(len(self.handler.new_stats())), z(self.table_words), z(2 * n_traces)
+                ids, off, spans, info = z(n_traces), z(n_traces + 1), z(8 * cap), z(native.DES_SPAN_INFO_WORDS)
+                tap = ds.make_tap(0, 0, native.Q_ALL, n_traces, cap, ids.data_ptr(), off.data_ptr(), spans.data_ptr(),
+                                  info.data_ptr())
+                self.serve_spans_device(trace_begin, n_traces, rec.data_ptr() if n_traces else 0, stats.data_ptr(),
+                                        table.data_ptr(), ws.data_ptr(), ws.numel() * 8, tap, stream, wide=w)
+                service_window_quantiles_device(self.handler, q, window_ns, n_windows, t0_ns, off.data_ptr(),
+                                                spans.data_ptr(), cap, info.data_ptr(), out.data_ptr(),
+                                                qws.data_ptr(), qws.numel() * 8, stream)
+                if not int(u64(stats)[native.ST_DES_RETRY]):
+                    break
+            h_info = u64(info)
+            h_out = u64(out)
+        self.last_tap_info = h_info
+        if int(h_info[native.DES_SPAN_MATCHES]) != int(h_info[native.SPAN_WRITTEN]):
+            raise RuntimeError(f"service_window_quantiles: the batch has {int(h_info[native.SPAN_TOTAL])} spans, "
+                               f"cap_spans {cap} holds {int(h_info[native.SPAN_WRITTEN])} of its "
+                               f"{int(h_info[native.DES_SPAN_MATCHES])} traces")
+        return ServiceWindowQuantiles(self.handler, q, window_ns, n_windows, t0_ns, h_out[:words].copy())
+
     def arrivals(self, trace_begin: int, n_traces: int, device: int = 0) -> np.ndarray:
         """The arrival times (u64 ns since batch start) `serve` uses for these traces."""
         if self.profile is not None:
