@@ -429,6 +429,16 @@ ISIM_API int isim_des_fold(const isim_handler *h, const uint64_t *des_table, uin
  * look-back fail at once, so tests can drive the error path.  Process-wide; read at each DES launch. */
 ISIM_API void isim_debug_set_spin_limit(uint32_t polls);
 ISIM_API uint32_t isim_debug_spin_limit(void);
+/* Test hooks (no reference counterpart), host only.  The first is the pure
+ * predicate a walk launch must meet to run the lean mode-A draw-stream kernel:
+ * 1 for a group table, kernel kind 4, mode A and one high word for all of the
+ * n_traces trace ids from trace_begin, else 0.  It does not know whether the
+ * device has that kernel (ISIM_NO_LEAN_WALK=1 or ISIM_NO_GROUP_TABLE=1 at
+ * device preparation leave it out).  The second counts the launches that did
+ * run it, process-wide, at launch (or capture) time. */
+ISIM_API int isim_debug_lean_walk_eligible(int has_table, uint32_t kernel_kind, int mode_b, uint64_t trace_begin,
+                                           uint64_t n_traces);
+ISIM_API uint64_t isim_debug_lean_walk_launches(void);
 
 /* ---- multi-device: trace shards + one RCCL all-reduce ----
  * north_star: traces shard evenly across the GPUs of a node; the histograms

@@ -26,6 +26,7 @@ namespace isim {
 // the kernel and its launch shape (walk_host.hip choose_kind, tune_shape)
 struct WalkShape {
   void *kernel = nullptr;
+  void *lean_kernel = nullptr;  // kind 4, mode A: the kernel of the launches that lean_walk_eligible admits (or none)
   uint32_t kind = 0;
   uint32_t mark_words = 0;  // kind 8: position marks per workgroup (records + the sentinel)
   uint32_t threads = 0;

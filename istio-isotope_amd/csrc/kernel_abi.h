@@ -288,6 +288,9 @@ constexpr uint32_t kHistWords = 2 * ISIM_N_PROM + 2 * ISIM_N_LOG2;
 // 8 draw stream + mode-B sparse ancestor marking (4, 5, 6, 8: stream_walk.h),
 // 7 lane tree walk (dynamic walks, tree.hip; `frames` = register stack depth).
 void *walk_kernel(int kind, bool modeb, bool lds_counters);
+// kind 4, mode A, for launches whose every batch draws from the group table
+// (walk_host.hip lean_walk_eligible): the table form of the chunk loop alone
+void *walk_kernel_lean(bool lds_counters);
 // kind 7 variant (tree.hip, compiled once per mode and concurrency):
 // register-stack depth (4, 6, 8, 12, 16; `spill`: 8 registers + the rest in
 // global memory), nodes in LDS or global, the error-block cache.

@@ -90,6 +90,9 @@ __device__ __forceinline__ void site_err_add(const Ctx &c, uint32_t slot, uint32
 // spill to VGPR lanes and come back as v_readlane (VALU).
 // NH per walker: what its kernels' VGPR budget (64 at ISIM_STREAM_WAVES 8)
 // holds with no scratch and no v_readlane added to a group loop.
+// What a held key saves is the SGPR source of its v_bitop3, not the s_add: a
+// VALU instruction that reads an SGPR costs the group loop more issue time
+// than one on VGPRs alone (measured on the lean kernel).
 #ifndef ISIM_HELD_A
 #define ISIM_HELD_A 4
 #endif
@@ -107,6 +110,22 @@ constexpr int kHeldMark = ISIM_HELD_MARK;    // walk_stream_mark (kind 8)
 constexpr int kHeldCl = ISIM_HELD_CL;        // walk_stream_cl (kind 6)
 constexpr int kHeldStack = ISIM_HELD_STACK;  // walk_stream (kinds 4 and 5, mode B)
 constexpr int kFirstKeyRound = 3;  // 0-based: rounds 0-1 scalar, round 2 keyless
+#ifndef ISIM_HELD_LEAN
+#define ISIM_HELD_LEAN 6
+#endif
+constexpr int kHeldLean = ISIM_HELD_LEAN;    // walk_stream_a, the lean kernel
+// The two Philox multipliers of the lockstep draws: the constants, or (LEAN)
+// wave-uniform VGPR values, opaque, so that the v_mad_u64_u32 of the group
+// loop read no SGPR either.
+template <bool LEAN>
+struct Mults {
+  static constexpr uint32_t m0 = M0, m1 = M1;
+};
+template <>
+struct Mults<true> {
+  uint32_t m0 = M0, m1 = M1;
+  __device__ __forceinline__ Mults() { asm volatile("" : "+v"(m0), "+v"(m1)); }
+};
 template <int NH>
 struct HeldKeys {
   static_assert(NH >= 0 && NH <= 10 - kFirstKeyRound, "rounds 4-10 take a key");
@@ -127,7 +146,11 @@ struct HeldKeys {
 // stream, so the per-record scalar work (fetch, decode, counter adds) is
 // shared and each lane runs TPL independent Philox chains (ILP).  Trace u of
 // a lane is trace base + 64 u + lane of the launch.
-template <int TPL, int NH>
+// LEAN (the lean mode-A kernel, which instantiates one chunk loop, not six,
+// and so has registers left): the keys of the rounds past NH are plain
+// loop-invariant sums of the seed words, which the compiler keeps in SGPRs,
+// not re-added per group, and the multipliers are VGPR values (Mults).
+template <int TPL, int NH, bool LEAN = false>
 struct StreamBatch {
   uint64_t idx[TPL], all[TPL];  // index in the launch; ballot of valid
   uint32_t t_lo[TPL], t_hi[TPL];
@@ -140,6 +163,7 @@ struct StreamBatch {
   // its use, the compiler re-associates the xor chain and pays a second xor
   // per trace in every group
   uint32_t bk[TPL];
+  Mults<LEAN> mul;
 
   __device__ __forceinline__ StreamBatch(const Ctx &c, uint64_t trace_begin, uint64_t n_traces, uint64_t base)
       : keys(c.k0, c.k1) {
@@ -191,8 +215,8 @@ __host__ __device__ __forceinline__ void philox_uniform_rounds(uint32_t t_hi_u, 
 // TPL Philox blocks (one per trace of the lane) of counter (t_lo[u], t_hi, g, 0)
 // in lockstep, given rounds 1-2 of the wave-uniform words (uk0, uk1, dk): the
 // round keys are shared by the TPL chains.
-template <int TPL, int NH>
-__device__ __forceinline__ void philox_lockstep_from(const StreamBatch<TPL, NH> &bt, uint32_t k0a, uint32_t k1a,
+template <int TPL, int NH, bool LEAN>
+__device__ __forceinline__ void philox_lockstep_from(const StreamBatch<TPL, NH, LEAN> &bt, uint32_t k0a, uint32_t k1a,
                                                      uint32_t uk0, uint32_t uk1, uint32_t dk, uint32_t (&x)[TPL][4]) {
   uint32_t a[TPL], b[TPL], cc[TPL], d[TPL];
   // round 3 without keys: k1 + 2 W1 is in dk and k0 + 2 W0 in the batch's bk.
@@ -206,8 +230,8 @@ __device__ __forceinline__ void philox_lockstep_from(const StreamBatch<TPL, NH> 
     const uint32_t bk = bt.bk[u];
     const uint32_t a2 = (uint32_t)(p1 >> 32) ^ uk0;
     const uint32_t c2 = (uint32_t)p0 ^ uk1;
-    const uint64_t r0 = (uint64_t)M0 * a2;
-    const uint64_t r1 = (uint64_t)M1 * c2;
+    const uint64_t r0 = (uint64_t)bt.mul.m0 * a2;
+    const uint64_t r1 = (uint64_t)bt.mul.m1 * c2;
     a[u] = (uint32_t)(r1 >> 32) ^ bk;
     b[u] = (uint32_t)r1;
     cc[u] = (uint32_t)(r0 >> 32) ^ dk;
@@ -216,9 +240,16 @@ __device__ __forceinline__ void philox_lockstep_from(const StreamBatch<TPL, NH> 
 #pragma unroll
   for (int i = 0; i < NH; ++i) {
 #pragma unroll
-    for (int u = 0; u < TPL; ++u) round1(a[u], b[u], cc[u], d[u], bt.keys.k0[i], bt.keys.k1[i]);
+    for (int u = 0; u < TPL; ++u) round1(a[u], b[u], cc[u], d[u], bt.keys.k0[i], bt.keys.k1[i], bt.mul.m0, bt.mul.m1);
   }
-  if constexpr (kFirstKeyRound + NH < 10) {
+  if constexpr (LEAN) {
+#pragma unroll
+    for (int r = kFirstKeyRound + NH; r < 10; ++r) {
+#pragma unroll
+      for (int u = 0; u < TPL; ++u) round1(a[u], b[u], cc[u], d[u], k0a + (uint32_t)r * W0, k1a + (uint32_t)r * W1,
+                                                   bt.mul.m0, bt.mul.m1);
+    }
+  } else if constexpr (kFirstKeyRound + NH < 10) {
     uint32_t k0 = k0a + (uint32_t)(kFirstKeyRound + NH) * W0;
     uint32_t k1 = k1a + (uint32_t)(kFirstKeyRound + NH) * W1;
 #pragma unroll
@@ -227,7 +258,7 @@ __device__ __forceinline__ void philox_lockstep_from(const StreamBatch<TPL, NH> 
       // compiler hoist them into SGPRs (HeldKeys)
       asm volatile("" : "+s"(k0), "+s"(k1));
 #pragma unroll
-      for (int u = 0; u < TPL; ++u) round1(a[u], b[u], cc[u], d[u], k0, k1);
+      for (int u = 0; u < TPL; ++u) round1(a[u], b[u], cc[u], d[u], k0, k1, bt.mul.m0, bt.mul.m1);
       k0 += W0;
       k1 += W1;
     }
@@ -286,8 +317,8 @@ __device__ __forceinline__ void stream_draws(const Ctx &c, const StreamBatch<TPL
 // The same draws from the group's table entry (the batch is hi_uniform and
 // its t_hi is the table's): no scalar rounds, and the threshold test is a bit
 // of the entry.
-template <int TPL, int NH>
-__device__ __forceinline__ void stream_draws_tab(const Ctx &c, const StreamBatch<TPL, NH> &bt, const GroupEnt &e,
+template <int TPL, int NH, bool LEAN>
+__device__ __forceinline__ void stream_draws_tab(const Ctx &c, const StreamBatch<TPL, NH, LEAN> &bt, const GroupEnt &e,
                                                  uint32_t (&x)[TPL][4]) {
   if (e.flags & kGroupAnyThr) {
     philox_lockstep_from<TPL, NH>(bt, c.k0, c.k1, e.uk0, e.uk1, e.d, x);
@@ -571,14 +602,20 @@ __device__ __forceinline__ void walk_stream(const Ctx &c, CNode4 *__restrict__ s
 // work).  No branch and no LDS operation per record; padding records and the
 // entry (no call site) are dropped at the flush.
 // FULL: every lane of every trace slot is valid.
+// LEAN (isim_walk<4, false, LDSC, true>): the host has checked that every
+// batch of the launch draws from the group table (walk_host.hip
+// lean_walk_eligible: a table, and one high word for all trace ids), so only
+// the table form of the chunk loop is instantiated.  With one loop instead of
+// three the kernel has the registers to take no round key and no multiplier
+// from an SGPR in the group loop (StreamBatch LEAN, kHeldLean).
 constexpr uint32_t kCountGroups = 64;  // groups per chunk: one lane each
-template <bool LDSC, int TPL, bool FULL>
+template <bool LDSC, int TPL, bool FULL, bool LEAN = false>
 __device__ __forceinline__ void walk_stream_a(const Ctx &c, CNode4 *__restrict__ stream, uint32_t n_groups,
                                               uint32_t n_nodes, uint64_t t_static, uint64_t trace_begin,
                                               uint64_t n_traces, uint64_t base,
                                               const uint32_t *__restrict__ stream_w, CEnt *__restrict__ tab,
                                               uint32_t tab_t_hi) {
-  const StreamBatch<TPL, kHeldA> bt(c, trace_begin, n_traces, base);
+  const StreamBatch<TPL, LEAN ? kHeldLean : kHeldA, LEAN> bt(c, trace_begin, n_traces, base);
   static_assert(64 * TPL < 256, "a record's 500 count is packed into a byte");
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   const uint32_t lane = lane_id();
@@ -590,7 +627,16 @@ __device__ __forceinline__ void walk_stream_a(const Ctx &c, CNode4 *__restrict__
   Node4 cur = load_group(stream);
   {  // record 0 is the entry invocation (the client request): its status is the trace's
     uint32_t x[TPL][4];
-    stream_draws(c, bt, bt.hi_uniform, ~0u, 0, x);
+    if constexpr (LEAN) {
+      // the table's t_hi is the valid lanes': an invalid lane of the last
+      // batch may lie past 2^32, and its draw is masked.  (With the scalar
+      // rounds here, as in the general kernel, the whole kernel was scheduled
+      // differently and config 3 ran 5 % slower: DESIGN.md §5.)
+      const GroupEnt e0 = load_ent(tab);
+      philox_lockstep_from(bt, c.k0, c.k1, e0.uk0, e0.uk1, e0.d, x);
+    } else {
+      stream_draws(c, bt, bt.hi_uniform, ~0u, 0, x);
+    }
 #pragma unroll
     for (int u = 0; u < TPL; ++u)
       root_st[u] = (cur.n[0].meta & 0x80000000u) ? bt.all[u] : (ballot(x[u][0] < cur.n[0].thr) & bt.all[u]);
@@ -669,9 +715,13 @@ __device__ __forceinline__ void walk_stream_a(const Ctx &c, CNode4 *__restrict__
       }
     }
   };
-  if (use_group_table(bt, tab, tab_t_hi)) chunks(std::integral_constant<int, 2>{});
-  else if (bt.hi_uniform) chunks(std::integral_constant<int, 1>{});
-  else chunks(std::integral_constant<int, 0>{});
+  if constexpr (LEAN) {
+    chunks(std::integral_constant<int, 2>{});
+  } else {
+    if (use_group_table(bt, tab, tab_t_hi)) chunks(std::integral_constant<int, 2>{});
+    else if (bt.hi_uniform) chunks(std::integral_constant<int, 1>{});
+    else chunks(std::integral_constant<int, 0>{});
+  }
 #pragma unroll
   for (int u = 0; u < TPL; ++u) bt.finish(c, u, t_static, n_nodes, root_st[u], errh[u]);
 }

@@ -527,10 +527,14 @@ __global__ void isim_group_table(const Node *__restrict__ stream, uint32_t n_gro
 // depth <= 32), 6 draw stream with the mode-B close list, 8 draw stream with
 // mode-B sparse ancestor marking (stream_walk.h; 7 is the lane tree walk, tree.hip)
 // LDSC: per-site counters in the workgroup LDS table (else global atomics)
-template <int KIND, bool MODEB, bool LDSC>
+// LEAN (KIND 4, mode A): every batch of the launch draws from the group table,
+// so walk_stream_a's table loop is the only one compiled in, and the group
+// loop takes its round keys and multipliers from VGPRs (stream_walk.h)
+template <int KIND, bool MODEB, bool LDSC, bool LEAN = false>
 __global__ void __launch_bounds__(kWgThreads, KIND >= 4 ? ISIM_STREAM_WAVES : 1)
     isim_walk(const Ins *__restrict__ prog, isim_trace_rec *__restrict__ records, uint64_t *__restrict__ gstats,
               const uint32_t *__restrict__ dur, KParams kp) {
+  static_assert(!LEAN || (KIND == 4 && !MODEB), "the lean kernel is mode A on the draw stream");
   using TT = typename std::conditional<KIND == 0 || KIND == 2, uint32_t, uint64_t>::type;
   constexpr bool STATIC = KIND < 2 || KIND >= 4;
   extern __shared__ __align__(16) unsigned char lds[];
@@ -609,6 +613,13 @@ __global__ void __launch_bounds__(kWgThreads, KIND >= 4 ? ISIM_STREAM_WAVES : 1)
       } else if constexpr (MODEB) {
         walk_stream<LDSC, kStreamTPL, KIND == 5>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base,
                                                  gt, gth);
+      } else if constexpr (LEAN) {
+        if (base + 64 * kStreamTPL <= kp.n_traces)
+          walk_stream_a<LDSC, kStreamTPL, true, true>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces,
+                                                      base, (const uint32_t *)prog, gt, gth);
+        else
+          walk_stream_a<LDSC, kStreamTPL, false, true>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces,
+                                                       base, (const uint32_t *)prog, gt, gth);
       } else if (base + 64 * kStreamTPL <= kp.n_traces)  // every lane of every trace slot valid
         walk_stream_a<LDSC, kStreamTPL, true>(c, st, ng, kp.n_nodes, kp.t_static, kp.trace_begin, kp.n_traces, base,
                                               (const uint32_t *)prog, gt, gth);
@@ -678,6 +689,10 @@ void *walk_kernel(int kind, bool modeb, bool lds_counters) {
       if (!modeb) return pick<4>(false, lds_counters);
       return lds_counters ? (void *)&dev::isim_walk<6, true, true> : (void *)&dev::isim_walk<6, true, false>;
   }
+}
+
+void *walk_kernel_lean(bool lds_counters) {
+  return lds_counters ? (void *)&dev::isim_walk<4, false, true, true> : (void *)&dev::isim_walk<4, false, false, true>;
 }
 
 void *mark_fold_kernel() { return (void *)&dev::isim_mark_fold; }

@@ -22,10 +22,11 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
   return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 }
 
+// m0, m1: the multipliers, for a caller that holds them in registers of its choice
 __device__ __forceinline__ void round1(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0,
-                                       uint32_t k1) {
-  const uint64_t p0 = (uint64_t)M0 * c0;
-  const uint64_t p1 = (uint64_t)M1 * c2;
+                                       uint32_t k1, uint32_t m0 = M0, uint32_t m1 = M1) {
+  const uint64_t p0 = (uint64_t)m0 * c0;
+  const uint64_t p1 = (uint64_t)m1 * c2;
   const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
   const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
   c0 = n0;

@@ -165,6 +165,20 @@ int tune_shape(const Program &p, const isim_params &params, const hipDeviceProp_
   return ISIM_OK;
 }
 
+// the lean mode-A kernel beside the general one: same workgroup, LDS and
+// grid.  It is built for the same waves per SIMD (63 VGPRs against 60); were
+// it ever less resident, the launches keep the general kernel.
+int tune_lean(WalkShape &sh) {
+  void *kern = walk_kernel_lean(sh.lds_counters != 0);
+  ISIM_HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)sh.lds_bytes));
+  int per_cu = 0;
+  ISIM_HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, (int)sh.threads,
+                                                           sh.lds_bytes));
+  if ((uint32_t)per_cu >= sh.per_cu) sh.lean_kernel = kern;
+  return ISIM_OK;
+}
+
 // the wave interpreters (kinds 0-3): the program and the per-slot duration words
 int upload_interp(const isim_handler *h, DevState &st) {
   const Program &p = h->prog;
@@ -173,7 +187,7 @@ int upload_interp(const isim_handler *h, DevState &st) {
 }
 
 // the draw stream (kinds 4, 5, 6, 8): the records, the slot multiplicities, mode B's tables, the launches' slots
-int upload_stream(const Program &p, DevState &st) {
+int upload_stream(const Program &p, bool modeb, DevState &st) {
   const WalkShape &sh = st.shape;
   // the kernel prefetches group g+1 unconditionally: two zero groups (32 B
   // each) of tail padding keep those reads inside the buffer
@@ -208,7 +222,11 @@ int upload_stream(const Program &p, DevState &st) {
   st.slots.gtab_groups = (p.stream_nodes + 3) / 4;
   const size_t tab_bytes = (size_t)(st.slots.gtab_groups + kGroupPad) * sizeof(GroupEnt) * kWorkSlots;
   const char *no_tab = std::getenv("ISIM_NO_GROUP_TABLE");
-  if (tab_bytes <= kGroupTableMaxBytes && !(no_tab && no_tab[0] == '1')) return alloc(st.slots.gtab, tab_bytes);
+  if (tab_bytes > kGroupTableMaxBytes || (no_tab && no_tab[0] == '1')) return ISIM_OK;
+  if (const int rc = alloc(st.slots.gtab, tab_bytes)) return rc;
+  // mode A: the lean kernel for the launches that can take it (ISIM_NO_LEAN_WALK=1, for tests: none)
+  const char *no_lean = std::getenv("ISIM_NO_LEAN_WALK");
+  if (sh.kind == 4 && !modeb && !(no_lean && no_lean[0] == '1')) return tune_lean(st.shape);
   return ISIM_OK;
 }
 
@@ -254,8 +272,9 @@ int build_device(isim_handler *h, int device, DevState &st) {
   const uint32_t lds_max = (uint32_t)std::max<size_t>(prop.sharedMemPerBlock, prop.maxSharedMemoryPerMultiProcessor);
   if (const int rc = tune_shape(p, h->params, prop, lds_max, choose_kind(p, h->params, lds_max), st.shape)) return rc;
   const uint32_t kind = st.shape.kind;
-  if (const int rc = is_stream(kind) ? upload_stream(p, st) : kind == 7 ? upload_tree(p, st) : upload_interp(h, st))
-    return rc;
+  const bool modeb = h->params.error_mode == ISIM_MODE_B;
+  const int rc = is_stream(kind) ? upload_stream(p, modeb, st) : kind == 7 ? upload_tree(p, st) : upload_interp(h, st);
+  if (rc != ISIM_OK) return rc;
   return upload(st.slots.work, nullptr, 0, (size_t)kWorkWords * kWorkSlots * sizeof(unsigned long long));
 }
 
@@ -271,6 +290,23 @@ uint64_t max_launch_traces(const WalkShape &sh) {
   if (sh.lds_counters) m = std::min<uint64_t>(m, std::max<uint64_t>(1, 0xFFFFFFFFull / sh.max_mult));
   return m;
 }
+
+}  // namespace
+
+// A launch takes the lean mode-A kernel when every one of its batches would
+// draw from the launch's group table in the general kernel: there is a table,
+// the walk is mode A on the draw stream, and the trace ids share the high
+// word the table is built for (so no batch straddles 2^32 or lies past it).
+bool lean_walk_eligible(bool has_table, uint32_t kind, bool modeb, uint64_t trace_begin, uint64_t n_traces) {
+  if (!has_table || kind != 4 || modeb || n_traces == 0) return false;
+  const uint64_t last = trace_begin + (n_traces - 1);
+  return last >= trace_begin && (trace_begin >> 32) == (last >> 32);
+}
+
+// launches that took the lean kernel, process-wide (isim_debug_lean_walk_launches)
+static uint64_t g_lean_launches = 0;
+
+namespace {
 
 int launch_walk_one(isim_handler *h, DevState *st, uint64_t trace_begin, uint64_t n_traces,
                     isim_trace_rec *d_records, uint64_t *d_stats, void *hip_stream) {
@@ -329,6 +365,12 @@ int launch_walk_one(isim_handler *h, DevState *st, uint64_t trace_begin, uint64_
                                 (hipStream_t)hip_stream));
   }
   void *args[] = {&prog, &d_records, &d_stats, &dur, &kp};
+  void *kernel = sh.kernel;
+  if (sh.lean_kernel && lean_walk_eligible(kp.gtab != nullptr, sh.kind, h->params.error_mode == ISIM_MODE_B,
+                                           trace_begin, n_traces)) {
+    kernel = sh.lean_kernel;
+    __atomic_fetch_add(&g_lean_launches, 1, __ATOMIC_RELAXED);
+  }
   if (tree.spill[0]) {
     // a spilling walk: the area its stream used last (else the next one,
     // round robin; allocated on first use), ordered after the area's previous
@@ -355,7 +397,7 @@ int launch_walk_one(isim_handler *h, DevState *st, uint64_t trace_begin, uint64_
     tree.spill_last[a] = hs;
     tree.spill_used[a] = true;
   } else {
-    ISIM_HIPCHK(hipLaunchKernel(sh.kernel, dim3(grid), dim3(sh.threads), args, sh.lds_bytes, (hipStream_t)hip_stream));
+    ISIM_HIPCHK(hipLaunchKernel(kernel, dim3(grid), dim3(sh.threads), args, sh.lds_bytes, (hipStream_t)hip_stream));
   }
   if (sh.kind == 8) {  // the launch's position marks into the per-site 500 counters
     uint32_t *row = kp.stage;
@@ -432,6 +474,13 @@ int prepare_device(isim_handler *h, int device, DevState *&out) {
 using isim::set_error;
 
 extern "C" {
+
+int isim_debug_lean_walk_eligible(int has_table, uint32_t kernel_kind, int mode_b, uint64_t trace_begin,
+                                  uint64_t n_traces) {
+  return isim::lean_walk_eligible(has_table != 0, kernel_kind, mode_b != 0, trace_begin, n_traces) ? 1 : 0;
+}
+
+uint64_t isim_debug_lean_walk_launches(void) { return __atomic_load_n(&isim::g_lean_launches, __ATOMIC_RELAXED); }
 
 int isim_handler_launch_info(isim_handler *h, int device, isim_launch_info *out) {
   if (!h || !out) return set_error(ISIM_EINVAL, "null argument");

@@ -248,6 +248,8 @@ SIGNATURES = {
     "isim_des_workers_get": (C.c_int, [_VP, _VP]),
     "isim_debug_set_spin_limit": (None, [C.c_uint32]),
     "isim_debug_spin_limit": (C.c_uint32, []),
+    "isim_debug_lean_walk_eligible": (C.c_int, [C.c_int, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64]),
+    "isim_debug_lean_walk_launches": (C.c_uint64, []),
     "isim_multi_get_id": (C.c_int, [C.POINTER(MultiId)]),
     "isim_multi_precheck": (C.c_int, [C.c_int]),
     "isim_multi_init_rank": (C.c_int, [C.POINTER(MultiId), C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
