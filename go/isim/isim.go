@@ -602,6 +602,89 @@ func (h *Handler) ServiceQuantilesHost(spans []DesSpan, qPpm []uint32) ([]uint64
 	return table, nil
 }
 
+// Per-service latency sketch (DESIGN §30): per service and measure (SvqWait,
+// SvqService, SvqDuration) a latency-sketch table by code and bin, then
+// SvqHeaderWords words.  Every word is a count: tables of many batches and
+// GPUs merge by addition.
+const (
+	SvsMaxWords = C.ISIM_SVS_MAX_WORDS
+	SvsShort    = C.ISIM_SVS_SHORT
+)
+
+// NewServiceSketch is a zeroed table of subBits (isim_service_sketch_table_words).
+func (h *Handler) NewServiceSketch(subBits uint32) ([]uint64, error) {
+	var words C.uint64_t
+	if err := lastErr(C.isim_service_sketch_table_words(h.h, C.uint32_t(subBits), &words)); err != nil {
+		return nil, err
+	}
+	return make([]uint64, words), nil
+}
+
+// ServiceSketch adds, on GPU `device`, spans (every span of a whole tapped
+// batch, in any order) into table, a NewServiceSketch of the same subBits
+// (isim_service_sketch).
+func (h *Handler) ServiceSketch(device int, subBits uint32, spans []DesSpan, table []uint64) error {
+	if err := h.serviceSketchTable(subBits, table); err != nil {
+		return err
+	}
+	var sp *C.isim_des_span
+	if len(spans) > 0 {
+		sp = (*C.isim_des_span)(unsafe.Pointer(&spans[0]))
+	}
+	return lastErr(C.isim_service_sketch(C.int(device), h.h, C.uint32_t(subBits), sp, C.uint64_t(len(spans)), u64ptr(table)))
+}
+
+// ServiceSketchHost is ServiceSketch on the CPU (isim_service_sketch_host).
+func (h *Handler) ServiceSketchHost(subBits uint32, spans []DesSpan, table []uint64) error {
+	if err := h.serviceSketchTable(subBits, table); err != nil {
+		return err
+	}
+	var sp *C.isim_des_span
+	if len(spans) > 0 {
+		sp = (*C.isim_des_span)(unsafe.Pointer(&spans[0]))
+	}
+	return lastErr(C.isim_service_sketch_host(h.h, C.uint32_t(subBits), sp, C.uint64_t(len(spans)), u64ptr(table)))
+}
+
+// ServiceSketchMerge adds every word of src to dst, the header included
+// (isim_service_sketch_merge).
+func (h *Handler) ServiceSketchMerge(subBits uint32, dst, src []uint64) error {
+	if err := h.serviceSketchTable(subBits, dst); err != nil {
+		return err
+	}
+	if err := h.serviceSketchTable(subBits, src); err != nil {
+		return err
+	}
+	return lastErr(C.isim_service_sketch_merge(h.h, C.uint32_t(subBits), u64ptr(dst), u64ptr(src)))
+}
+
+// ServiceSketchQuantiles gives, per service and measure, SketchQuantiles' words
+// of that block: [services][SvqMeasures][3 classes][1 + 2 * len(qPpm)], per class
+// the count, then lo and hi per quantile (isim_service_sketch_quantiles).
+func (h *Handler) ServiceSketchQuantiles(subBits uint32, table []uint64, qPpm []uint32) ([]uint64, error) {
+	if err := h.serviceSketchTable(subBits, table); err != nil {
+		return nil, err
+	}
+	blocks := (uint64(len(table)) - SvqHeaderWords) / (2 * ((65 - uint64(subBits)) << subBits))
+	out := make([]uint64, blocks*3*(1+2*uint64(len(qPpm)))+1)
+	if err := lastErr(C.isim_service_sketch_quantiles(h.h, C.uint32_t(subBits), u64ptr(table), u32ptr(qPpm), C.uint32_t(len(qPpm)), u64ptr(out))); err != nil {
+		return nil, err
+	}
+	return out[:len(out)-1], nil
+}
+
+// serviceSketchTable refuses a table that is not of this handler and subBits.
+func (h *Handler) serviceSketchTable(subBits uint32, table []uint64) error {
+	var words C.uint64_t
+	if err := lastErr(C.isim_service_sketch_table_words(h.h, C.uint32_t(subBits), &words)); err != nil {
+		return err
+	}
+	if uint64(len(table)) != uint64(words) {
+		return fmt.Errorf("isim: a service sketch of %d words, want %d", len(table), uint64(words))
+	}
+	return nil
+}
+
 // Per-service percentiles over time (DESIGN §29): per service, timeline row
 // (0 before t0Ns, 1 .. nWindows the windows, nWindows + 1 after; the row of a
 // span's finish), measure and class a cell of 1 + len(qPpm) words as in

@@ -1444,6 +1444,83 @@ ISIM_API int isim_service_window_quantiles(int device, const isim_handler *h, co
                                            const uint32_t *q_ppm, uint32_t n_q, const isim_des_span *h_spans,
                                            uint64_t n_spans, uint64_t *h_out);
 
+/* ---- per-service latency sketch: percentiles across batches and GPUs (EXT) ----
+ * The mergeable counterpart of isim_service_quantiles: for every service one
+ * isim_latency_sketch table per measure, filled from the isim_des_span records
+ * of a tapped batch (threshold 0: every executed invocation).  Exact order
+ * statistics need every span of the population in one buffer; these words are
+ * counts, so tables of many batches and GPUs merge by addition, and a quantile
+ * comes back as the bracket of isim_sketch_quantiles.
+ *
+ * A span is refused by the rule of isim_service_timeline: service >=
+ * n_services, or a <= S <= F does not hold (a = arrival_ns, S = start_ns,
+ * F = finish_ns).  A refused span counts in ISIM_SVQ_H_REFUSED and in nothing
+ * else; the host and the device refuse the same spans.  Measures ISIM_SVQ_WAIT
+ * / ISIM_SVQ_SERVICE / ISIM_SVQ_DURATION: isim_service_quantiles'.  The code is
+ * status bit 0.
+ *
+ * The table: u64 [n_services][ISIM_SVQ_MEASURES][2][ISIM_SK_BINS(s)], then a
+ * header of ISIM_SVQ_HEADER_WORDS words (ISIM_SVQ_H_FOLDED, ISIM_SVQ_H_REFUSED).
+ * Each [2][ISIM_SK_BINS(s)] block is a table of isim_latency_sketch, indexed by
+ * code then bin, s = sub_bits in 0 .. ISIM_SK_MAX_SUB_BITS: isim_sketch_bucket,
+ * isim_sketch_bounds, isim_sketch_merge (n_rows = 3 * n_services, the header
+ * apart) and isim_sketch_quantiles apply to it unchanged.  A span that is not
+ * refused adds 1 to one word of each of its service's three blocks.
+ *
+ * The table is ACCUMULATED INTO, the header included: the caller zeroes it
+ * once, and a call adds only to the words it hits.  A batch the engine did not
+ * accumulate (d_off[0] = 0, nothing written) adds nothing.  Tables merge by
+ * plain addition of every word (a SUM all-reduce of the raw words across GPUs;
+ * no RCCL entry point, as for isim_latency_sketch). */
+#define ISIM_SVS_MAX_WORDS (1ull << 32)   /* a table of this many words or more is refused: a word index fits the
+                                             u32 the peel compares; 100,000 services at s = 3 are 297,600,002 */
+/* The device call adds a service with at most ISIM_SVS_SHORT spans straight
+ * into the table, whole services per wave; a longer one is cut into chunks of
+ * ISIM_SVQ_CHUNK elements, each histogrammed in LDS by one workgroup. */
+#define ISIM_SVS_SHORT 256
+
+/* Every call below returns ISIM_EINVAL, before any HIP call, for a handler
+ * isim_service_quantiles refuses and a null argument; those that take sub_bits
+ * for sub_bits above ISIM_SK_MAX_SUB_BITS and for a table of ISIM_SVS_MAX_WORDS
+ * words or more at that sub_bits; those that take a span count for more than
+ * ISIM_SVQ_MAX_SPANS spans. */
+/* host only, no GPU: n_services * 3 * 2 * ISIM_SK_BINS(sub_bits) + ISIM_SVQ_HEADER_WORDS */
+ISIM_API int isim_service_sketch_table_words(const isim_handler *h, uint32_t sub_bits, uint64_t *words);
+/* host only, no GPU.  With P(x) = x rounded up to a multiple of 256:
+ *   256 + 3 * P(8 * n_services)                        per service: counts, offsets and cursors by (service, code)
+ *   + 24 * cap_spans                                   per span: its three measures, scattered by service
+ *   + L * ISIM_SVQ_SLOT_BYTES                          per long segment: its record
+ * where L = min(n_services, cap_spans / (ISIM_SVS_SHORT + 1)) is the most long segments cap_spans spans can form.
+ * It does not depend on sub_bits (the long segments' bins are in LDS), so the table's bound is not this call's. */
+ISIM_API int isim_service_sketch_workspace_bytes(const isim_handler *h, uint64_t cap_spans, uint64_t *bytes);
+/* host only, no GPU: dst[i] += src[i] for every word of the table, the header included */
+ISIM_API int isim_service_sketch_merge(const isim_handler *h, uint32_t sub_bits, uint64_t *dst, const uint64_t *src);
+/* host only, no GPU: out is u64 [n_services][ISIM_SVQ_MEASURES][ISIM_SKQ_OUT_WORDS(n_q)], isim_sketch_quantiles of
+ * each (service, measure) block, with its errors (the quantile list, a class count above 2^40) */
+ISIM_API int isim_service_sketch_quantiles(const isim_handler *h, uint32_t sub_bits, const uint64_t *table,
+                                           const uint32_t *q_ppm, uint32_t n_q, uint64_t *out);
+/* Adds the spans that a preceding isim_serve_des_spans_device wrote to d_spans
+ * into d_table, on the current device, asynchronously on hip_stream.  The
+ * spans are addressed as isim_service_quantiles_device addresses them: the
+ * count is read on the device, d_off[d_info[ISIM_SPAN_WRITTEN]], bounded by
+ * cap_spans (which sizes the grids and the workspace); d_off and d_info are the
+ * tap's.  A fixed sequence of kernels that does not depend on the data: no
+ * host synchronisation, no allocation, graph-capturable from the first call,
+ * the workspace may be dirty (calls that share one, or one table, must be
+ * ordered).  cap_spans 0 touches nothing and needs no workspace.  Also
+ * ISIM_EINVAL: buffers not 8-byte aligned (d_spans 16), a workspace below
+ * isim_service_sketch_workspace_bytes. */
+ISIM_API int isim_service_sketch_device(const isim_handler *h, uint32_t sub_bits, const uint64_t *d_off,
+                                        const isim_des_span *d_spans, uint64_t cap_spans, const uint64_t *d_info,
+                                        uint64_t *d_table, void *d_workspace, uint64_t workspace_bytes,
+                                        void *hip_stream);
+/* host only, no GPU: the same fold on the CPU over h_spans[0 .. n_spans), a plain loop; ADDS into h_table */
+ISIM_API int isim_service_sketch_host(const isim_handler *h, uint32_t sub_bits, const isim_des_span *h_spans,
+                                      uint64_t n_spans, uint64_t *h_table);
+/* Synchronous convenience: host buffers, on GPU `device`; ADDS into h_table. */
+ISIM_API int isim_service_sketch(int device, const isim_handler *h, uint32_t sub_bits, const isim_des_span *h_spans,
+                                 uint64_t n_spans, uint64_t *h_table);
+
 #ifdef __cplusplus
 }
 #endif

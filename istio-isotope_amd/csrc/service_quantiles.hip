@@ -19,7 +19,8 @@
 //   and leave when there is nothing for them.
 // The select itself, in LDS and as launches, is segmented_select.h's; the span
 // load, the count, the scatter and the long segments' kernels are
-// span_segments.h's, which service_window_quantiles.hip (§29) shares.
+// span_segments.h's, which service_window_quantiles.hip (§29) shares; the scan
+// is service_scan.h's, which service_sketch.hip (§30) shares.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,57 +28,12 @@
 
 #include "hip_check.h"
 #include "host_stage.h"
+#include "service_scan.h"
 #include "span_segments.h"
 
 namespace isim {
 namespace svq {
 namespace {
-
-constexpr uint32_t kScanThreads = 1024;
-
-// One workgroup, a service per thread and tile: the exclusive scan of the counts into the segment offsets and
-// the scatter cursors; the long segments get a slot each, in service order, and the first of their chunks.
-// The counts are of at most cap spans, so no more than n_slots segments are long.
-__global__ __launch_bounds__(kScanThreads) void k_svq_scan(const uint32_t *__restrict__ cnt, uint32_t *__restrict__ off,
-                                                          uint32_t *__restrict__ cur, uint32_t n_services, Slot *slots,
-                                                          uint32_t n_slots, Head *head) {
-  __shared__ uint32_t s_wave[kScanThreads / 64];
-  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-  uint32_t c_elem = 0, c_long = 0, c_chunk = 0;
-  for (uint32_t tile = 0; tile < n_services; tile += kScanThreads) {
-    const uint32_t s = tile + t;
-    const bool live = s < n_services;
-    const uint32_t n200 = live ? cnt[2 * s] : 0u, n500 = live ? cnt[2 * s + 1] : 0u;
-    const uint32_t n = n200 + n500;
-    const bool is_long = n > kStage;
-    uint32_t t_elem, t_long, t_chunk;
-    const uint32_t e = c_elem + rs::block_scan<kScanThreads>(n, s_wave, lane, wave, t_elem);
-    const uint32_t l = c_long + rs::block_scan<kScanThreads>(is_long ? 1u : 0u, s_wave, lane, wave, t_long);
-    const uint32_t c =
-        c_chunk + rs::block_scan<kScanThreads>(is_long ? (n - 1) / kChunk + 1 : 0u, s_wave, lane, wave, t_chunk);
-    if (live) {
-      off[2 * s] = cur[2 * s] = e;
-      off[2 * s + 1] = cur[2 * s + 1] = e + n200;
-      if (is_long && l < n_slots) {
-        Slot &x = slots[l];
-        x.svc = s;
-        x.chunk0 = c;
-        x.n200 = n200;
-        x.n500 = n500;
-        x.off = e;
-        for (uint32_t m = 0; m < kMeasures; ++m) x.any[m] = 0;
-      }
-    }
-    c_elem += t_elem;
-    c_long += t_long;
-    c_chunk += t_chunk;
-  }
-  if (t == 0) {
-    const bool fits = c_long <= n_slots;  // always, for counts of at most cap spans
-    head->n_long = fits ? c_long : 0u;
-    head->n_chunks = fits ? c_chunk : 0u;
-  }
-}
 
 // The short segments.  A workgroup claims services through the ticket until none is left.  An empty service
 // gets its zeros, a long one is the long kernels'.  Otherwise, per measure, the segment is staged in LDS and
@@ -162,7 +118,7 @@ int launch(uint32_t n_services, const uint32_t *q_ppm, uint32_t n_q, const uint6
                      (uint32_t *)ws, clear_words, (uint32_t *)k.hdr, (uint64_t)2 * ISIM_SVQ_HEADER_WORDS);
   const uint32_t grid = rs::grid_for(cap_spans, kThreads * kUnroll, kMaxGrid);
   hipLaunchKernelGGL(k_svq_count<ServiceKey>, dim3(grid), dim3(kThreads), 0, s, k, ServiceKey{});
-  hipLaunchKernelGGL(k_svq_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t *)k.cnt, (uint32_t *)(ws + l.off),
+  hipLaunchKernelGGL(k_svq_scan<kStage>, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t *)k.cnt, (uint32_t *)(ws + l.off),
                      k.cur, n_services, a.slots, a.n_slots, a.head);
   hipLaunchKernelGGL(k_svq_scatter<ServiceKey>, dim3(grid), dim3(kThreads), 0, s, k, ServiceKey{});
   hipLaunchKernelGGL(k_svq_short, dim3(std::min(n_services, kSelMaxGrid)), dim3(kSelThreads), 0, s, a);

@@ -34,6 +34,9 @@ from .service_timeline import (ServiceTimeline, service_holds, service_timeline,
 from .service_quantiles import (MEASURE_NAMES, ServiceQuantiles, decode_service_quantiles,  # noqa: F401
                                 service_quantiles, service_quantiles_device, service_quantiles_host,
                                 service_quantiles_table_words, service_quantiles_workspace_bytes)
+from .service_sketch import (ServiceSketch, service_sketch, service_sketch_device, service_sketch_host,  # noqa: F401
+                             service_sketch_merge, service_sketch_quantiles, service_sketch_table_words,
+                             service_sketch_workspace_bytes)
 from .service_window_quantiles import (ServiceWindowQuantiles, decode_service_window_quantiles,  # noqa: F401
                                        service_window_quantiles, service_window_quantiles_device,
                                        service_window_quantiles_host, service_window_quantiles_table_words,

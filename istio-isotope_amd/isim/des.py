@@ -309,6 +309,52 @@ class DesHandler:
                                f"{int(h_info[native.DES_SPAN_MATCHES])} traces")
         return ServiceQuantiles(self.handler, q, h_out[:words].copy())
 
+    def service_sketch(self, trace_begin: int, n_traces: int, sub_bits: int = 3, device: int = 0, into=None,
+                       cap_spans: int = None):
+        """The ServiceSketch of one batch, added into `into` (a ServiceSketch of this handler
+        and sub_bits; a new one if None) and returned: the whole batch tapped as service_quantiles taps it
+        and sketched on the same stream; only the batch's table comes back.  32-bit rows first, and again
+        wide if the batch asks for it (the first attempt wrote no span and added nothing).  Raises if the
+        spans did not fit cap_spans, and then `into` is unchanged.  Item engine only."""
+        import torch
+        from . import des_spans as ds
+        from .service_sketch import (ServiceSketch, service_sketch_device, service_sketch_table_words,
+                                     service_sketch_workspace_bytes)
+        n_traces = int(n_traces)
+        if into is not None and (into.sub_bits != int(sub_bits) or into.handler is not self.handler):
+            raise ValueError("service_sketch: `into` is a sketch of another handler or sub_bits")
+        cap = n_traces * int(self.handler.info.hops_upper) if cap_spans is None else int(cap_spans)
+        words = service_sketch_table_words(self.handler, sub_bits)
+        kws_bytes = service_sketch_workspace_bytes(self.handler, cap)
+        dev = torch.device("cuda", device)
+        u64 = lambda t: t.cpu().numpy().view(np.uint64)  # noqa: E731
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            z = lambda n: torch.zeros(max(1, n), dtype=torch.int64, device=dev)  # noqa: E731
+            ws = z(self.workspace_bytes(n_traces) // 8 + 1)
+            kws = torch.empty(max(1, kws_bytes // 8 + 1), dtype=torch.int64, device=dev)
+            for w in [False, True]:
+                out = z(words)  # this attempt's own table: a retried attempt leaves nothing behind
+                stats, table, rec = z(len(self.handler.new_stats())), z(self.table_words), z(2 * n_traces)
+                ids, off, spans, info = z(n_traces), z(n_traces + 1), z(8 * cap), z(native.DES_SPAN_INFO_WORDS)
+                tap = ds.make_tap(0, 0, native.Q_ALL, n_traces, cap, ids.data_ptr(), off.data_ptr(), spans.data_ptr(),
+                                  info.data_ptr())
+                self.serve_spans_device(trace_begin, n_traces, rec.data_ptr() if n_traces else 0, stats.data_ptr(),
+                                        table.data_ptr(), ws.data_ptr(), ws.numel() * 8, tap, stream, wide=w)
+                service_sketch_device(self.handler, sub_bits, off.data_ptr(), spans.data_ptr(), cap, info.data_ptr(),
+                                      out.data_ptr(), kws.data_ptr(), kws.numel() * 8, stream)
+                if not int(u64(stats)[native.ST_DES_RETRY]):
+                    break
+            h_info = u64(info)
+            h_out = u64(out)
+        self.last_tap_info = h_info
+        if int(h_info[native.DES_SPAN_MATCHES]) != int(h_info[native.SPAN_WRITTEN]):
+            raise RuntimeError(f"service_sketch: the batch has {int(h_info[native.SPAN_TOTAL])} spans, cap_spans "
+                               f"{cap} holds {int(h_info[native.SPAN_WRITTEN])} of its "
+                               f"{int(h_info[native.DES_SPAN_MATCHES])} traces")
+        batch = ServiceSketch(self.handler, sub_bits, h_out[:words].copy())
+        return batch if into is None else into.merge(batch)
+
     def service_window_quantiles(self, trace_begin: int, n_traces: int, q=DEFAULT_Q, window_ns: int = 1_000_000,
                                  n_windows: int = 100, t0_ns: int = 0, device: int = 0, cap_spans: int = None):
         """The ServiceWindowQuantiles of one batch: the whole batch tapped as service_timeline

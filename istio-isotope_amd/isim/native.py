@@ -102,6 +102,9 @@ SVQ_MAX_SPANS = 0xFFFFFFFF
 SVQ_STAGE = 3584
 SVQ_CHUNK = 4096
 SVQ_SLOT_BYTES = 3584
+# isim_service_sketch*: the table's bound and the short tier's segment size (isim.h ISIM_SVS_*)
+SVS_MAX_WORDS = 1 << 32
+SVS_SHORT = 256
 # isim_service_window_quantiles*: the bound on services x rows and the wave tier's segment size (isim.h ISIM_SWQ_*)
 SWQ_MAX_CELLS = 1 << 20
 SWQ_WAVE = 256
@@ -347,6 +350,13 @@ SIGNATURES = {
                                                 C.c_uint64, _VP]),
     "isim_service_quantiles_host": (C.c_int, [_VP, _VP, C.c_uint32, _VP, C.c_uint64, _VP]),
     "isim_service_quantiles": (C.c_int, [C.c_int, _VP, _VP, C.c_uint32, _VP, C.c_uint64, _VP]),
+    "isim_service_sketch_table_words": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "isim_service_sketch_workspace_bytes": (C.c_int, [_VP, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "isim_service_sketch_merge": (C.c_int, [_VP, C.c_uint32, _VP, _VP]),
+    "isim_service_sketch_quantiles": (C.c_int, [_VP, C.c_uint32, _VP, _VP, C.c_uint32, _VP]),
+    "isim_service_sketch_device": (C.c_int, [_VP, C.c_uint32, _VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_uint64, _VP]),
+    "isim_service_sketch_host": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint64, _VP]),
+    "isim_service_sketch": (C.c_int, [C.c_int, _VP, C.c_uint32, _VP, C.c_uint64, _VP]),
     "isim_service_window_quantiles_table_words": (C.c_int, [_VP, C.POINTER(TimelineParams), C.c_uint32,
                                                             C.POINTER(C.c_uint64)]),
     "isim_service_window_quantiles_workspace_bytes": (C.c_int, [_VP, C.POINTER(TimelineParams), C.c_uint64, C.c_uint32,
